@@ -15,11 +15,14 @@ and a handful of warm-up steps must cover that.  N>1: one process per GPU, every
 environment) or, run plainly as `python bench.py --gpus N`, from this script itself: before anything touches the
 GPU it starts N children of itself with those variables set (launch_ranks), relays rank 0's line and fails when
 any child does -- the crawler's own fan-out of one self-contained task per file (Crawler.cpp:706-728) one level up.
-After the replica measurement ONE process (rank 0) drives all N devices through the C++ file-sharding crawler
+With --full, after the replica measurement ONE process (rank 0) drives all N devices through the C++ file-sharding crawler
 (afec::TCrawler, file i -> device i mod N: the analogue of Crawler.cpp:706-728) over BASELINE configs[3] -- 12 500 x N
 stereo one-second WAV images -- and the line carries that as config.sharded_crawl.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the `--steps` steps, writes what the last of them
+computed when `--dump-outputs DIR` is given, and prints the line.  Everything else the line can carry -- the parity spot
+check against the oracle, the shader clock sampled during a repeat of the timed launches, the secondary rates, the C3 / C4
+chains, the end-to-end host driver, config.sharded_crawl and the CPU baseline -- runs with `--full` only.
 """
 import argparse
 import json
@@ -86,7 +89,13 @@ def parse_args():
     ap.add_argument("--no-clock-probe", action="store_true", help="do not sample the shader clock during the timed launches")
     ap.add_argument("--no-sharded-crawl", action="store_true", help="skip config.sharded_crawl (rank 0 driving all N devices)")
     ap.add_argument("--no-chain-rates", action="store_true",
-                    help="skip the C3 / C4-share chain rates (BASELINE configs[2] / [3]) of the default line")
+                    help="skip the C3 / C4-share chain rates (BASELINE configs[2] / [3]) of the --full line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: parity spot check, in-run shader clock, secondary rates, C3 / C4 "
+                         "chains, end-to-end host driver, sharded crawl, CPU baseline (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy in float64; "
+                         "a fixed, seeded sample of rows when the whole would exceed %d MiB" % (DUMP_BUDGET_BYTES >> 20))
     # test hook of the launcher (tests/test_bench_dist_cpu.py): this rank exits with status 7 before it joins the others
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--stall-seconds", type=float, default=0.0, help=argparse.SUPPRESS)   # test hook: every rank sleeps first
@@ -179,6 +188,42 @@ def launch_ranks(n_gpus, argv, poll_s=0.05):
 
 DISTINCT_BUFFERS = 64   # mt19937 buffers generated on the host; larger batches tile them (every copy has its own place in HBM)
 C2_SEED = 1234          # std::mt19937(1234)
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: at most this much in all (the sample's rows are fixed by the shapes alone)
+
+
+def caller_outputs(batch, mask):
+    """What a caller of the timed path receives from the batch as it stands: the per-frame descriptors and per-buffer
+    offsets / status (afx_batch_fetch), the per-file statistics ("stats_<name>"), the rhythm tracker's output
+    ("rhythm_<name>").  A BatchSet's batches are joined in file order, their offsets made global."""
+    joined = {}
+    for b in (batch.batches if isinstance(batch, BatchSet) else [batch]):
+        res = b.fetch()
+        if mask & afx.D_STATISTICS:
+            res.update({("stats_status" if k == "stats_status" else "stats_" + k): v for k, v in b.fetch_statistics().items()})
+        if mask & afx.D_RHYTHM:
+            res.update({"rhythm_" + k: v for k, v in b.fetch_rhythm().items()})
+        for k, v in res.items():
+            if k in ("frame_offset", "rhythm_offsets") and k in joined:
+                v = v[1:] + joined[k][-1][-1]
+            joined.setdefault(k, []).append(v)
+    return {k: np.concatenate(v) for k, v in joined.items()}
+
+
+def dump_outputs(outputs, out_dir):
+    """outputs -> out_dir/<name>.npy as float64.  When the whole exceeds DUMP_BUDGET_BYTES every array keeps the same
+    fraction of its rows, drawn without replacement by a generator seeded from the array's name, in row order."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 8 for a in outputs.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / total) if total else 1.0
+    for name, a in sorted(outputs.items()):
+        a = np.asarray(a, dtype=np.float64)
+        if keep < 1.0 and a.ndim > 0 and a.shape[0] > 1:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a[np.sort(rng.choice(a.shape[0], size=max(1, int(a.shape[0] * keep)), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def mt19937_uniform(n, seed):
@@ -762,6 +807,8 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: the line would report another job than the one asked for")
 
     if args.end_to_end:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes a resident batch's outputs; --end-to-end has none")
         if args.workload == "c2":
             args.workload = "c4"
         device = int(os.environ.get("AFX_BENCH_DEVICE", local))
@@ -844,10 +891,12 @@ def main():
     t1 = time.perf_counter()
     if dist is not None:
         dist.barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(caller_outputs(batch, mask), args.dump_outputs)
     # the shader clock under this load, sampled in this very process during a repeat of the K launches (clock_during says
     # why not during the timed region itself): the VALU ceiling of the roofline object is priced at the clock of this run
     clock = None
-    if not args.no_clock_probe and not isinstance(batch, BatchSet):
+    if args.full and not args.no_clock_probe and not isinstance(batch, BatchSet):
         clock = clock_during(lambda: batch.run_timed(args.steps), device, step_estimate_s * args.steps)[0]
         if dist is not None:
             dist.barrier()
@@ -859,7 +908,7 @@ def main():
     # What the timed launches left in HBM is checked, not only timed: the MFCC of 64 frames of three buffers of this
     # very batch against the oracle (the checker, after the timed region; tests/_tol.py's bar for the descriptor)
     spot = None
-    if rank == 0 and spot_bufs and (mask & afx.D_MFCC) and not args.no_spot_check:
+    if args.full and rank == 0 and spot_bufs and (mask & afx.D_MFCC) and not args.no_spot_check:
         try:
             spot = parity_spot_check(batch, spot_bufs, FRAMES_PER_BUFFER)
         except Exception as e:  # noqa: BLE001
@@ -867,13 +916,13 @@ def main():
     batch.close()
     batch = None
     headline = args.workload == "c2" and args.mask == "c2"
-    secondaries = rank == 0 and world == 1 and headline and not args.no_single   # single-GPU diagnostics of the default line
+    secondaries = args.full and rank == 0 and world == 1 and headline and not args.no_single   # single-GPU diagnostics of the --full line
 
     # N > 1: ONE process now drives all N devices through the C++ file-sharding crawler (the replicas above
     # scale by construction).  Every rank has given its batch back; ranks > 0 also their plan (pooled workspaces) and wait.
     sharded = None
     pinned = int(os.environ["AFX_BENCH_DEVICE"]) if "AFX_BENCH_DEVICE" in os.environ else None
-    want_sharded = headline and not args.no_sharded_crawl
+    want_sharded = args.full and headline and not args.no_sharded_crawl
     if want_sharded and world > 1:
         if rank != 0:
             plan.close()
@@ -1093,7 +1142,7 @@ def main():
                 "launch_ms": launch_ms,
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             t_cpu = time.time()
             out["cpu_baseline"] = cpu_baseline(args.cpu_frames)
             out["cpu_baseline"]["seconds"] = time.time() - t_cpu

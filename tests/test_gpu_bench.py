@@ -26,7 +26,7 @@ def test_gpus_2_run_plainly_starts_two_ranks_and_counts_both():
     """`python bench.py --gpus 2` the way the driver runs `--gpus 1`: no WORLD_SIZE in the environment.  Both ranks are
     pinned to the one device of this box (AFX_BENCH_DEVICE): the line must say two ranks, name them, and count the
     frames of both -- not measure one GPU and call it n_gpus 1."""
-    common = ("--buffers", "16", "--steps", "3", "--no-cpu-baseline", "--no-single")
+    common = ("--buffers", "16", "--steps", "3", "--full", "--no-cpu-baseline", "--no-single")
     one = _bench_line("--gpus", "1", *common)
     two = _bench_line("--gpus", "2", *common, env={"AFX_BENCH_DEVICE": "0"})
     assert one["n_gpus"] == 1 and one["ranks_seen"] == [0]
@@ -94,10 +94,10 @@ def test_chain_rate_objects_of_the_line(workload, n_files, mask_name, batch_file
 
 
 def test_the_default_line_one_gpu_sharded_crawl_agrees_with_the_end_to_end_driver():
-    """The driver's own command (minus the CPU baseline): config.sharded_crawl at N = 1 is the same C++ driver over one
+    """The driver's --full command (minus the CPU baseline): config.sharded_crawl at N = 1 is the same C++ driver over one
     device and must agree with config.end_to_end_host_driver; the roofline carries the clock of this very run and the
     VALU fraction at that clock and at the nominal one; the two round-6 chain objects are there with their spot checks."""
-    line = _bench_line("--no-cpu-baseline")
+    line = _bench_line("--full", "--no-cpu-baseline")
     roof, cfg = line["roofline"], line["config"]
     assert 1.0 < roof["clock_ghz_in_run"] < 2.6 and roof["clock_probe"]["ended_by"] == "stop"
     if roof["valu"] is not None:      # counters are quoted for the build they were measured on only
@@ -113,6 +113,33 @@ def test_the_default_line_one_gpu_sharded_crawl_agrees_with_the_end_to_end_drive
         assert cfg[key]["parity_spot_check"]["passed"], (key, cfg[key]["parity_spot_check"])
     assert cfg["c4_share_at_crawler_shape"]["frame_kernel"] == "wave64"
     assert "mt19937" in cfg["workload"]
-    # the driver's default run has to finish within minutes: every secondary object of the line included (the CPU
+    # the driver's --full run has to finish within minutes: every secondary object of the line included (the CPU
     # baseline, not run here, adds its bounded ~20 s; profiles/r06/bench_default.json)
     assert line["run_seconds"] < 150, line["run_seconds"]
+
+
+def test_a_plain_line_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain run (no --full) carries the headline alone -- no spot check, in-run clock, secondary objects or CPU
+    baseline -- and --dump-outputs writes what the last timed step left in HBM: with 16 buffers the whole MFCC (160 000 x
+    14 float64, inside the budget), whose first 64 frames of buffer 0 are the oracle's within the bar."""
+    import numpy as np
+    line = _bench_line("--buffers", "16", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["unit"] == "frames/s" and line["dtype"] == "f64"
+    assert abs(line["value"] - 16 * 10000 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    cfg = line["config"]
+    assert cfg["parity_spot_check"] is None and cfg["sharded_crawl"] is None and cfg["c3_frames_per_s"] is None
+    assert cfg["end_to_end_host_driver"] is None and line["roofline"]["clock_probe"] is None and "cpu_baseline" not in line
+    names = sorted(os.listdir(tmp_path))
+    assert names == ["buf_status.npy", "frame_offset.npy", "mfcc.npy"]
+    assert sum(os.path.getsize(tmp_path / n) for n in names) <= 64 << 20
+    mfcc = np.load(tmp_path / "mfcc.npy")
+    assert mfcc.dtype == np.float64 and mfcc.shape == (16 * 10000, 14)
+    np.testing.assert_array_equal(np.load(tmp_path / "frame_offset.npy"), np.arange(17) * 10000.0)
+    sys.path.insert(0, ROOT)
+    import bench
+    from tests import _tol
+    from tests._oracle import Oracle
+    x = bench.make_buffers(1, bench.C2_SEED)[0]
+    ref = Oracle().run_mfcc(x[:2048 + 1024 * 63].astype(np.float64))
+    rtol, atol = _tol.GPU_TOL["mfcc"]
+    _tol.check_gpu("mfcc", mfcc[:64], ref, rtol, atol, what="bench dump ")

@@ -4,12 +4,9 @@
 2. the reference's own known-answer tests for TStatistics
    (Source/Crawler/FeatureExtraction/Test/TestStatistics.cpp:10-115);
 3. the survey's known-answer values for a 1 kHz sine (SURVEY.md section 8c);
-4. when oracle/_ref/ref_driver is present (build container), a live comparison on fresh inputs.
+4. three further seeded buffers against the reference's frames of them (tests/golden/spot.npz, make_golden_spot.py).
 """
 import os
-import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -18,7 +15,6 @@ from tests import _oracle, _tol
 from tests._oracle import FIELDS, Oracle
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-REF_DRIVER = os.path.join(_oracle.ROOT, "oracle", "_ref", "ref_driver")
 
 # oracle (radix-2 FFT) vs reference (Ooura split radix): both IEEE double; bins agree to a few
 # ulp of the frame's largest bin, so descriptors that take logs of leakage-floor bins agree to
@@ -143,21 +139,11 @@ def test_calc_statistics_short_series():
     assert out[2] == 3 and out[3] == 3.5 and abs(out[11] - 1.0) < 1e-15 and out[12] == 0
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DRIVER), reason="reference objects only exist in the build container")
 def test_oracle_matches_live_reference(oracle):
-    rng = np.random.default_rng(7)
-    bufs = [rng.uniform(-1, 1, 2048 + 1024 * 5), 0.3 * rng.standard_normal(5000),
-            np.sin(2 * np.pi * 3000 * np.arange(9000) / 44100) * np.linspace(1, 0, 9000)]
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "i"), os.path.join(d, "o")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<q", len(bufs)))
-            for b in bufs:
-                f.write(struct.pack("<q", b.size))
-                f.write(b.astype(np.float64).tobytes())
-        subprocess.check_call([REF_DRIVER, "frames", fin, fout, "0"])
-        raw = open(fout, "rb").read()
-    ref = np.frombuffer(raw[8:], dtype=np.float64).reshape(-1, _oracle.RECORD)
+    """the seeded buffers of tests/golden/make_golden_spot.py against the reference's frames of them (`ref_driver frames`)"""
+    from tests.golden.make_golden_spot import frames_buffers
+    bufs = frames_buffers()
+    ref = np.load(os.path.join(GOLD, "spot.npz"))["frames"]
     got = np.concatenate([oracle.run(b) for b in bufs])
     assert got.shape == ref.shape
     _tol.check_mag(got[:, :1024], ref[:, :1024], 1e-13)

@@ -11,8 +11,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
-def plain_builds():
-    out = subprocess.run([os.path.join(ROOT, "tests", "sanitize", "build.sh"), "plain"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+def san_env(tmp_path_factory):
+    """build.sh writes into a directory of this session's own (AFX_SAN_DIR), not into a fixed one another user may own"""
+    return dict(os.environ, AFX_SAN_DIR=str(tmp_path_factory.mktemp("afx_san")))
+
+
+@pytest.fixture(scope="module")
+def plain_builds(san_env):
+    out = subprocess.run([os.path.join(ROOT, "tests", "sanitize", "build.sh"), "plain"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600,
+                         env=san_env)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     return {os.path.basename(p).replace("_plain", ""): p for p in out.stdout.decode().split()}
 
@@ -39,13 +46,12 @@ def test_the_c_abi_host_code_on_the_mock_device(plain_builds):
     assert b"clean" in r.stdout
 
 
-def test_the_mock_restates_the_launch_rules_of_the_product_library():
+def test_the_mock_restates_the_launch_rules_of_the_product_library(tmp_path):
     """frames_use_halfwave / frames32_class / frames_feature_class / ... live in the .hip files; mock_kernels.cpp restates
     them.  The product library can be loaded without a GPU: both must agree on every mask the planner can produce."""
     import afec_amd
     real = ctypes.CDLL(afec_amd.library_path())
-    so = "/tmp/afx_san/libmock_rules.so"
-    os.makedirs("/tmp/afx_san", exist_ok=True)
+    so = str(tmp_path / "libmock_rules.so")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", "-I" + os.path.join(ROOT, "tests", "sanitize", "hipstub"),
                            "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "sanitize", "mock_kernels.cpp"),
                            os.path.join(ROOT, "tests", "sanitize", "hipstub", "hip_stub.cpp"), "-o", so])
@@ -78,13 +84,14 @@ def test_the_mock_restates_the_launch_rules_of_the_product_library():
         assert real._ZN3afx15resample_blocksEl(n) == mock._ZN3afx15resample_blocksEl(n)
 
 
-def test_the_bench_lines_sharded_crawl_on_eight_mock_devices(tmp_path):
+def test_the_bench_lines_sharded_crawl_on_eight_mock_devices(tmp_path, san_env):
     """bench.py's config.sharded_crawl as an 8-GPU node would run it -- one process, afec_amd/hostlib.py ->
     afec_crawl_wave_images_ex -> afec::TCrawler over devices 0..7 -- with the mock device under the same host sources
     (build.sh's host_lib target, injected into hostlib from the test, never reachable from the product): the per-device
     arrays the Python side sizes by the number of devices, file i -> device i mod 8, workers per device from the CPU
     quota, and the same row digest for the same content on every device."""
-    out = subprocess.run([os.path.join(ROOT, "tests", "sanitize", "build.sh"), "plain", "host_lib"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    out = subprocess.run([os.path.join(ROOT, "tests", "sanitize", "build.sh"), "plain", "host_lib"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600,
+                         env=san_env)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     mock = out.stdout.decode().split()[-1]
     script = tmp_path / "crawl8.py"

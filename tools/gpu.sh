@@ -5,10 +5,10 @@
 #   record                       the GPU suite with AFX_TOL_RECORD: the worst relative error of every descriptor over every
 #                                check_gpu() call (tests/_tol.py; ceilings not enforced)  -> $O/observed_errors.json
 #   bench[=<bench.py args>]      one bench.py line (default: the driver's)           -> $O/bench_default.json
-#   gpus2                        `bench.py --gpus 2` run plainly, both ranks on device 0 -> $O/bench_gpus2.json
+#   gpus2                        `bench.py --gpus 2 --full` run plainly, both ranks on device 0 -> $O/bench_gpus2.json
 #   profile=<tag>[,<args>]       tools/profile_config.py <tag> <args>  (kernel trace + PMC passes)
 #   profiles                     every configuration of profiles/kernel_profiles.json
-#   lease                        ONE lease, one record: the driver's bench line, then every profile, then tools/lease_report.py
+#   lease                        ONE lease, one record: the driver's --full bench line, then every profile, then tools/lease_report.py
 #                                (host name, the line's rates and in-run clocks beside the profiled kernel times of c2 / c3 / c4)
 #                                                                                     -> $O/lease_report.{json,txt}
 #   ab=<bench args>@<lib>,<lib>  steady per-kernel durations of builds under afec_amd/lib/<lib>/ (kernel trace only)
@@ -40,7 +40,7 @@ for STAGE in "$@"; do
       timeout 900 python bench.py $ARG > $O/bench_default.json 2> $O/bench_default.err
       echo "rc=$?"; tail -c 600 $O/bench_default.json; echo; tail -3 $O/bench_default.err ;;
     gpus2)
-      AFX_BENCH_DEVICE=0 timeout 600 python bench.py --gpus 2 --no-cpu-baseline --no-single > $O/bench_gpus2.json 2> $O/bench_gpus2.err
+      AFX_BENCH_DEVICE=0 timeout 600 python bench.py --gpus 2 --full --no-cpu-baseline --no-single > $O/bench_gpus2.json 2> $O/bench_gpus2.err
       echo "rc=$?"; head -c 700 $O/bench_gpus2.json; echo; tail -3 $O/bench_gpus2.err ;;
     profile)
       TAG=${ARG%%,*}; REST=""; [ "$ARG" != "$TAG" ] && REST=${ARG#*,}
@@ -57,7 +57,7 @@ for STAGE in "$@"; do
       python tools/profile_config.py c4_crawler --workload c4 --mask frame --batch-files 512 --in-flight 5 --frame-kernel wave64 | head -12 ;;
     lease)
       hostname > $O/lease_host.txt; date -u +%FT%TZ >> $O/lease_host.txt
-      timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+      timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err
       echo "bench rc=$?"; tail -2 $O/bench_default.err
       bash $0 profiles
       python tools/lease_report.py | tee $O/lease_report.txt ;;
