@@ -18,6 +18,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -67,9 +68,6 @@ struct TCrawlOptions {
   // files at another sampling rate than the analyser's are converted on the GPU like the reference converts them on
   // the CPU (SampleAnalyser.cpp:563-607, libresample; afx_resample.hip); false: they are skipped and counted
   bool mResample = true;
-  // with a database: the workers build the rows' column values (msgpack BLOBs: ~12 % of the single writer's time per
-  // row), the writer only binds and steps; false: the writer does both
-  bool mPrepareRowsInWorkers = true;
   // a batch is also cut (before it is tried) when the device memory its files need -- their samples *after* the
   // sample-rate conversion, spectra, records -- exceeds this: a header that claims 1 kHz makes a small file a large one
   int64_t mDeviceBytesPerBatch = (int64_t)2 << 30;
@@ -141,7 +139,7 @@ public:
 
 private:
   struct TImpl;
-  TImpl* mpImpl;
+  std::unique_ptr<TImpl> mpImpl;
 };
 
 }  // namespace afec
@@ -153,10 +151,7 @@ extern "C" {
 // stats: [files, failed, frames, pcm_bytes, result_bytes, seconds, writer_seconds, batches, files on device 0, 1, ...,
 // cpu_seconds, files skipped for their sampling rate, retried batches, files failed on the device] (8 + n_devices + 4 doubles);
 // returns 0, or -1 with the message in error.
-int afec_crawl_wave_images(const char* const* names, const void* const* images, const int64_t* sizes, int32_t n_files,
-                           const int32_t* devices, int32_t n_devices, int32_t workers_per_device, int32_t files_per_batch,
-                           const char* database_path, double* stats, char* error, int32_t error_size);
-// The same with the per-device figures and the row digests of a sharded crawl: device_stats (NULL or [n_devices][3]) =
+// Beside stats, the per-device figures and the row digests of a sharded crawl: device_stats (NULL or [n_devices][3]) =
 // {files, bytes of PCM uploaded, seconds until the device's last batch was delivered} per device; row_digests (NULL or
 // [n_files]) = TCrawlStatistics::mRowDigests; crawl_facts (NULL or [3]) = {worker threads per device the crawl ran with,
 // UsableHostCpus(), 1 when afec_crawl_request_abort ended the crawl early}.  workers_per_device <= 0: TCrawlOptions' default (picked from the usable CPUs and the device count).
@@ -180,7 +175,7 @@ int afec_wave_probe_file(const char* path, int64_t* props /* [7] */, void* paylo
                          int32_t error_size);
 int afec_shard_of_file(int64_t file_index, int32_t n_devices);
 void afec_crawl_release(void);
-// ends the crawl that is running through afec_crawl_wave_images / _ex early (TCrawlOptions::mpAbortRequested; the
+// ends the crawl that is running through afec_crawl_wave_images_ex early (TCrawlOptions::mpAbortRequested; the
 // reference's SIGINT handler, Crawler.cpp:69-73): safe from another thread or a signal handler; cleared when a crawl starts
 void afec_crawl_request_abort(void);
 // TCrawlOptions::mBytesPerBatch of the crawls that follow (0: the default)

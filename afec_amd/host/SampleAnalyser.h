@@ -142,10 +142,16 @@ public:
                                           std::vector<std::string>* pFailed = nullptr) const;
 
   // LoadSample + descriptors + statistics for decoded files, results left as raw records in caller memory:
-  // pRecords must hold RecordCapacity doubles, pStatistics Files.size() * 134 * 13 (kMaxStride columns), pRhythm
+  // pRecords must hold RecordCapacity doubles, pStatistics Files.size() * kMaxStride * kStatisticsPerSeries, pRhythm
   // RhythmCapacity doubles (RhythmDoubles() of the files is always enough).  Returns false (and leaves Batch empty)
   // when the records do not fit RecordCapacity or the rhythm results RhythmCapacity: call again with larger buffers.
-  enum { kMaxStride = 134 };
+  enum {
+    kMaxStride = 134,                                 // columns of a per-frame record at most (TRecordBatch::mStride)
+    kStatisticsPerSeries = 13,                        // TStatistics::Calc's values per column (AFX_NUM_STATISTICS)
+    kRhythmScalars = 14,                              // TRecordBatch::mpRhythmScalars per file (AFX_NUM_RHYTHM_SCALARS)
+    kRhythmStatistics = 2 * kStatisticsPerSeries,     // TRecordBatch::mpRhythmStatistics per file: the two onset series'
+    kRhythmDoublesPerFile = kRhythmScalars + kRhythmStatistics   // what a file adds to the rhythm buffer besides its onset rows
+  };
   size_t RhythmDoubles(const std::vector<TDecodedSample>& Files) const;
   // does the analyser's device still answer (afx_plan_probe_device)?  false after a fault that took the context down:
   // nothing more can be analysed, as opposed to a batch that failed for its own reasons (memory, a bad file)

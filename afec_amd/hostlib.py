@@ -17,10 +17,6 @@ def _bind(L):
     L.afec_wave_probe_file.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_char_p, ctypes.c_int32]
     L.afec_shard_of_file.argtypes = [ctypes.c_int64, ctypes.c_int32]
-    L.afec_crawl_wave_images.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_void_p),
-                                         ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
-                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
-                                         ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int32]
     L.afec_crawl_wave_images_ex.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_void_p),
                                             ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
