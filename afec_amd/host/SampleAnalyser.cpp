@@ -5,7 +5,7 @@
 #include <chrono>
 #include <cmath>
 
-#include "../../include/afx.h"
+#include "DescriptorTable.h"
 
 namespace afec {
 
@@ -32,93 +32,94 @@ void TSampleAnalyser::SetSleepingWaits(bool Sleeping) { afx_plan_set_blocking_wa
 int64_t TSampleAnalyser::NumberOfFrames(int64_t NumberOfSamples) const { return afx_num_frames(mpPlan, NumberOfSamples); }
 
 namespace {
+
+void FillStrided(TFramedScalarData& Dst, const double* pSrc, int64_t Frames, int Stride) {
+  Dst.mValues.resize((size_t)Frames);
+  for (int64_t f = 0; f < Frames; ++f) Dst.mValues[(size_t)f] = pSrc[f * Stride];
+}
 template <int W>
-void Fill(TFramedVectorData<W>& Dst, const double* pSrc, int64_t Frames) {
+void FillStrided(TFramedVectorData<W>& Dst, const double* pSrc, int64_t Frames, int Stride) {
   Dst.mValues.resize((size_t)Frames);
   for (int64_t f = 0; f < Frames; ++f)
-    for (int b = 0; b < W; ++b) Dst.mValues[(size_t)f][b] = pSrc[f * W + b];
+    for (int b = 0; b < W; ++b) Dst.mValues[(size_t)f][b] = pSrc[f * Stride + b];
 }
-void Fill(TFramedScalarData& Dst, const double* pSrc, int64_t Frames) { Dst.mValues.assign(pSrc, pSrc + Frames); }
-}  // namespace
-
-namespace {
-// the 13 values of TStatistics::Calc in the order of AFX_S_* -> the members of the framed data
+// [13] (per band: [W][13]) values of TStatistics::Calc -> the members of the framed data
 void FillStatistics(TFramedScalarData& Dst, const double* pS) {
-  Dst.mMin = pS[AFX_S_MIN]; Dst.mMax = pS[AFX_S_MAX]; Dst.mMedian = pS[AFX_S_MEDIAN]; Dst.mMean = pS[AFX_S_MEAN];
-  Dst.mGeometricMean = pS[AFX_S_GMEAN]; Dst.mVariance = pS[AFX_S_VARIANCE]; Dst.mCentroid = pS[AFX_S_CENTROID];
-  Dst.mSpread = pS[AFX_S_SPREAD]; Dst.mSkewness = pS[AFX_S_SKEWNESS]; Dst.mKurtosis = pS[AFX_S_KURTOSIS];
-  Dst.mFlatness = pS[AFX_S_FLATNESS]; Dst.mDMean = pS[AFX_S_DMEAN]; Dst.mDVariance = pS[AFX_S_DVARIANCE];
+  ForEachStatistic<TFramedScalarData>([&](const char*, int k, auto pMember) { Dst.*pMember = pS[k]; });
 }
 template <int W>
 void FillStatistics(TFramedVectorData<W>& Dst, const double* pS) {
-  for (int b = 0; b < W; ++b) {
-    const double* p = pS + (size_t)b * AFX_NUM_STATISTICS;
-    Dst.mMin[b] = p[AFX_S_MIN]; Dst.mMax[b] = p[AFX_S_MAX]; Dst.mMedian[b] = p[AFX_S_MEDIAN]; Dst.mMean[b] = p[AFX_S_MEAN];
-    Dst.mGeometricMean[b] = p[AFX_S_GMEAN]; Dst.mVariance[b] = p[AFX_S_VARIANCE]; Dst.mCentroid[b] = p[AFX_S_CENTROID];
-    Dst.mSpread[b] = p[AFX_S_SPREAD]; Dst.mSkewness[b] = p[AFX_S_SKEWNESS]; Dst.mKurtosis[b] = p[AFX_S_KURTOSIS];
-    Dst.mFlatness[b] = p[AFX_S_FLATNESS]; Dst.mDMean[b] = p[AFX_S_DMEAN]; Dst.mDVariance[b] = p[AFX_S_DVARIANCE];
-  }
+  for (int b = 0; b < W; ++b)
+    ForEachStatistic<TFramedVectorData<W>>(
+        [&](const char*, int k, auto pMember) { (Dst.*pMember)[b] = pS[(size_t)b * AFX_NUM_STATISTICS + k]; });
 }
 
-// one series of the ABI: per-frame values and per-buffer statistics, and where they go in TSampleDescriptors
-struct TScalarSeries {
-  double* afx_out::*mpOut;
-  double* afx_stats_out::*mpStat;
-  TFramedScalarData TSampleDescriptors::*mpDst;
-};
-template <int W>
-struct TVectorSeries {
-  double* afx_out::*mpOut;
-  double* afx_stats_out::*mpStat;
-  TFramedVectorData<W> TSampleDescriptors::*mpDst;
-};
-#define AFEC_SERIES(abi, member) {&afx_out::abi, &afx_stats_out::abi, &TSampleDescriptors::member}
-const TScalarSeries kScalarSeries[] = {
-    AFEC_SERIES(amplitude_silence, mAmplitudeSilence), AFEC_SERIES(amplitude_peak, mAmplitudePeak),
-    AFEC_SERIES(amplitude_rms, mAmplitudeRms), AFEC_SERIES(amplitude_envelope, mAmplitudeEnvelope),
-    AFEC_SERIES(spectral_rms, mSpectralRms), AFEC_SERIES(spectral_centroid, mSpectralCentroid),
-    AFEC_SERIES(spectral_rolloff, mSpectralRolloff), AFEC_SERIES(spectral_spread, mSpectralSpread),
-    AFEC_SERIES(spectral_skewness, mSpectralSkewness), AFEC_SERIES(spectral_kurtosis, mSpectralKurtosis),
-    AFEC_SERIES(spectral_flatness, mSpectralFlatness), AFEC_SERIES(spectral_inharmonicity, mSpectralInharmonicity),
-    AFEC_SERIES(spectral_complexity, mSpectralComplexity), AFEC_SERIES(spectral_contrast, mSpectralContrast),
-    AFEC_SERIES(spectral_flux, mSpectralFlux), AFEC_SERIES(f0, mF0), AFEC_SERIES(f0_confidence, mF0Confidence),
-    AFEC_SERIES(failsafe_f0, mFailSafeF0), AFEC_SERIES(tristimulus1, mTristimulus1),
-    AFEC_SERIES(tristimulus2, mTristimulus2), AFEC_SERIES(tristimulus3, mTristimulus3),
-    AFEC_SERIES(auto_correlation, mAutoCorrelation)};
-const TVectorSeries<14> kSubBandSeries[] = {
-    AFEC_SERIES(sub_rms, mSpectralRmsBands), AFEC_SERIES(sub_flatness, mSpectralFlatnessBands),
-    AFEC_SERIES(sub_flux, mSpectralFluxBands), AFEC_SERIES(sub_complexity, mSpectralComplexityBands),
-    AFEC_SERIES(sub_contrast, mSpectralContrastBands), AFEC_SERIES(mfcc, mCepstrumBands)};
-const TVectorSeries<28> kBandSeries[] = {AFEC_SERIES(spectrum_bands, mSpectrumBands)};
-#undef AFEC_SERIES
+// file mFile of a TRecordBatch -> TSampleDescriptors, entry by entry of the table
+struct TFromRecords {
+  using D = TSampleDescriptors;
+  const TRecordBatch& mBatch;
+  const int mFile;
+  D& mResult;
+  const bool mWithRhythm = !mBatch.mRhythmOffset.empty() && mBatch.mpRhythmScalars;
 
-// the rhythm tracker's results of file i (afx_batch_fetch_rhythm layout) -> TSampleDescriptors
-void FillRhythm(TSampleDescriptors& R, int i, const int64_t* pOffset, const double* pOnsets, const double* pScalars,
-                const double* pStatistics) {
-  const int64_t t0 = pOffset[i], nt = pOffset[i + 1] - t0;
-  R.mRhythmComplexOnsets.mValues.resize((size_t)nt);
-  R.mRhythmPercussiveOnsets.mValues.resize((size_t)nt);
-  for (int64_t t = 0; t < nt; ++t) {
-    R.mRhythmComplexOnsets.mValues[(size_t)t] = pOnsets[(t0 + t) * 2];
-    R.mRhythmPercussiveOnsets.mValues[(size_t)t] = pOnsets[(t0 + t) * 2 + 1];
+  void EffectiveLength(const char*, int j, double D::*pMember) { mResult.*pMember = mBatch.mEffectiveLength[(size_t)mFile * 3 + j]; }
+  void AnalyzationOffset(const char*) {}
+  template <class T>
+  void Series(const char*, int k, T D::*pMember) {
+    const int Offset = mBatch.mOffsets[k], Stride = mBatch.mStride;
+    if (Offset < 0) return;   // not in the batch's mask
+    const int64_t f0 = mBatch.mFrameOffset[(size_t)mFile], nf = mBatch.mFrameOffset[(size_t)mFile + 1] - f0;
+    FillStrided(mResult.*pMember, mBatch.mpRecords + f0 * Stride + Offset, nf, Stride);
+    FillStatistics(mResult.*pMember, mBatch.mpStatistics + ((size_t)mFile * Stride + Offset) * AFX_NUM_STATISTICS);
   }
-  FillStatistics(R.mRhythmComplexOnsets, pStatistics + (size_t)i * 2 * AFX_NUM_STATISTICS);
-  FillStatistics(R.mRhythmPercussiveOnsets, pStatistics + ((size_t)i * 2 + 1) * AFX_NUM_STATISTICS);
-  const double* s = pScalars + (size_t)i * AFX_NUM_RHYTHM_SCALARS;
-  R.mRhythmComplexOnsetCount = s[AFX_R_COMPLEX_ONSET_COUNT];
-  R.mRhythmComplexTempo = s[AFX_R_COMPLEX_TEMPO];
-  R.mRhythmComplexTempoConfidence = s[AFX_R_COMPLEX_TEMPO_CONFIDENCE];
-  R.mRhythmComplexOnsetFrequencyMean = s[AFX_R_COMPLEX_ONSET_FREQUENCY_MEAN];
-  R.mRhythmComplexOnsetStrength = s[AFX_R_COMPLEX_ONSET_STRENGTH];
-  R.mRhythmComplexOnsetContrast = s[AFX_R_COMPLEX_ONSET_CONTRAST];
-  R.mRhythmPercussiveOnsetCount = s[AFX_R_PERCUSSIVE_ONSET_COUNT];
-  R.mRhythmPercussiveTempo = s[AFX_R_PERCUSSIVE_TEMPO];
-  R.mRhythmPercussiveTempoConfidence = s[AFX_R_PERCUSSIVE_TEMPO_CONFIDENCE];
-  R.mRhythmPercussiveOnsetFrequencyMean = s[AFX_R_PERCUSSIVE_ONSET_FREQUENCY_MEAN];
-  R.mRhythmPercussiveOnsetStrength = s[AFX_R_PERCUSSIVE_ONSET_STRENGTH];
-  R.mRhythmPercussiveOnsetContrast = s[AFX_R_PERCUSSIVE_ONSET_CONTRAST];
-  R.mRhythmFinalTempo = s[AFX_R_FINAL_TEMPO];
-  R.mRhythmFinalTempoConfidence = s[AFX_R_FINAL_TEMPO_CONFIDENCE];
+  void Onsets(const char*, int j, TFramedScalarData D::*pMember) {
+    if (!mWithRhythm) return;
+    const int64_t t0 = mBatch.mRhythmOffset[(size_t)mFile], nt = mBatch.mRhythmOffset[(size_t)mFile + 1] - t0;
+    FillStrided(mResult.*pMember, mBatch.mpRhythmOnsets + t0 * 2 + j, nt, 2);
+    FillStatistics(mResult.*pMember, mBatch.mpRhythmStatistics + ((size_t)mFile * 2 + j) * AFX_NUM_STATISTICS);
+  }
+  void RhythmScalar(const char*, int k, double D::*pMember) {
+    if (mWithRhythm) mResult.*pMember = mBatch.mpRhythmScalars[(size_t)mFile * AFX_NUM_RHYTHM_SCALARS + k];
+  }
+};
+
+}  // namespace
+
+TSampleDescriptors TRecordBatch::Descriptors(int i) const {
+  TSampleDescriptors R;
+  ForEachLowLevel(TFromRecords{*this, i, R});
+  return R;
+}
+
+// The whole of AnalyzeLowLevelDescriptors' loop (SampleAnalyser.cpp:814-976) and of CalcStatistics
+// (SampleAnalyser.cpp:1065, 2402-2412) runs on the GPU: every per-frame series and its 13 statistics come
+// back from one resident batch.
+namespace {
+
+constexpr uint32_t kEverything = AFX_D_ALL_PER_FRAME | AFX_D_EFFECTIVE_LENGTH | AFX_D_RHYTHM | AFX_D_STATISTICS;
+
+struct TBatchGuard {
+  afx_batch* mpBatch = nullptr;
+  ~TBatchGuard() { afx_batch_destroy(mpBatch); }
+};
+
+double Now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+std::vector<TSampleDataInfo> InfoOf(const std::vector<afx_load_info>& Info) {
+  std::vector<TSampleDataInfo> Result(Info.size());
+  for (size_t i = 0; i < Info.size(); ++i) Result[i] = {Info[i].peak_value, Info[i].rms_value, Info[i].data_offset, Info[i].n_samples};
+  return Result;
+}
+
+// decoded files -> a batch whose LoadSample front end has run; Info[i] is what it found
+void CreateFromFiles(afx_plan* pPlan, const std::vector<TDecodedSample>& Files, TBatchGuard& Batch, std::vector<afx_load_info>& Info) {
+  std::vector<afx_raw> Raws(Files.size());
+  for (size_t i = 0; i < Files.size(); ++i)
+    Raws[i] = {Files[i].mpInterleavedSamples, Files[i].mFormat, Files[i].mNumberOfChannels, Files[i].mSampleRate, 0,
+               Files[i].mNumberOfSampleFrames};
+  Info.resize(Files.size());
+  const int Status = afx_batch_create_from_raw(pPlan, Raws.data(), (int32_t)Files.size(), kEverything, &Batch.mpBatch, Info.data());
+  if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
 }
 
 // TSampleData::mOriginalSampleRate / mOriginalNumberOfSamples of files the caller resampled (SampleAnalyser.cpp:464-467)
@@ -135,18 +136,60 @@ int SetFileInfo(afx_batch* pBatch, const std::vector<TDecodedSample>& Files, con
   return afx_batch_set_file_info(pBatch, FileInfo.data());
 }
 
-struct TBatchGuard {
-  afx_batch* mpBatch = nullptr;
-  ~TBatchGuard() { afx_batch_destroy(mpBatch); }
-};
-}  // namespace
+// The record layout of a created batch and the doubles its results take (both known before it runs): records
+// [frames][stride]; rhythm = onsets [rows][2] + scalars [n][14] + onset statistics [n][2][13].  The statistics take
+// n * stride * 13.
+struct TResultDoubles { size_t mRecords, mRhythm; };
+TResultDoubles Layout(afx_batch* pBatch, int32_t n, TRecordBatch& Result) {
+  Result = TRecordBatch();
+  afx_batch_record_layout(pBatch, &Result.mStride, Result.mOffsets, Result.mWidths);
+  Result.mRhythmOffset.resize((size_t)n + 1);
+  const size_t RhythmRows = (size_t)afx_batch_rhythm_frames(pBatch, Result.mRhythmOffset.data());
+  return {(size_t)afx_batch_total_frames(pBatch) * (size_t)Result.mStride,
+          RhythmRows * 2 + (size_t)n * TSampleAnalyser::kRhythmDoublesPerFile};
+}
 
-// The whole of AnalyzeLowLevelDescriptors' loop (SampleAnalyser.cpp:814-976) and of CalcStatistics
-// (SampleAnalyser.cpp:1065, 2402-2412) runs on the GPU: every per-frame series and its 13 statistics come
-// back from one resident batch.
-namespace {
-constexpr uint32_t kEverything = AFX_D_ALL_PER_FRAME | AFX_D_EFFECTIVE_LENGTH | AFX_D_RHYTHM | AFX_D_STATISTICS;
-std::vector<TSampleDescriptors> Collect(TBatchGuard& Batch, int32_t n, std::vector<std::string>* pFailed);
+// (file info ->) run -> everything the batch computed into the caller's buffers, sized as Layout() says, and Result
+// pointing into them; pFiles: the decoded files of CreateFromFiles, if any
+void RunAndFetch(afx_batch* pBatch, int32_t n, const std::vector<TDecodedSample>* pFiles, const std::vector<afx_load_info>& Info,
+                 int PlanRate, double* pRecords, double* pStatistics, double* pRhythm, TRecordBatch& Result) {
+  const double t1 = Now();
+  int Status = pFiles ? SetFileInfo(pBatch, *pFiles, Info, PlanRate) : AFX_OK;
+  if (Status == AFX_OK) Status = afx_batch_run(pBatch);
+  if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
+  const double t2 = Now();
+  Result.mFrameOffset.resize((size_t)n + 1);
+  Result.mStatus.resize((size_t)n);
+  Result.mEffectiveLength.resize((size_t)n * 3);
+  Status = afx_batch_fetch_records(pBatch, pRecords, pStatistics, Result.mFrameOffset.data(), Result.mStatus.data(),
+                                   Result.mEffectiveLength.data());
+  double* const pOnsets = pRhythm;
+  double* const pScalars = pOnsets + (size_t)Result.mRhythmOffset.back() * 2;
+  double* const pOnsetStatistics = pScalars + (size_t)n * AFX_NUM_RHYTHM_SCALARS;
+  if (Status == AFX_OK) Status = afx_batch_fetch_rhythm(pBatch, pOnsets, pScalars, pOnsetStatistics);
+  if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
+  Result.mpRecords = pRecords; Result.mpStatistics = pStatistics;
+  Result.mpRhythmOnsets = pOnsets; Result.mpRhythmScalars = pScalars; Result.mpRhythmStatistics = pOnsetStatistics;
+  Result.mInfo = InfoOf(Info);
+  Result.mSeconds[1] = t2 - t1; Result.mSeconds[2] = Now() - t2;
+}
+
+// the same into buffers of its own, every file materialised: what Analyze and AnalyzeLowLevelDescriptors return
+std::vector<TSampleDescriptors> RunAndCollect(afx_batch* pBatch, int32_t n, const std::vector<TDecodedSample>* pFiles,
+                                              const std::vector<afx_load_info>& Info, int PlanRate, std::vector<std::string>* pFailed) {
+  TRecordBatch Batch;
+  const TResultDoubles Doubles = Layout(pBatch, n, Batch);
+  std::vector<double> Records(Doubles.mRecords), Statistics((size_t)n * (size_t)Batch.mStride * AFX_NUM_STATISTICS), Rhythm(Doubles.mRhythm);
+  RunAndFetch(pBatch, n, pFiles, Info, PlanRate, Records.data(), Statistics.data(), Rhythm.data(), Batch);
+  std::vector<TSampleDescriptors> Results((size_t)n);
+  if (pFailed) pFailed->assign((size_t)n, std::string());
+  for (int32_t i = 0; i < n; ++i) {
+    if (Batch.mStatus[(size_t)i] == AFX_OK) Results[(size_t)i] = Batch.Descriptors(i);
+    else if (pFailed) (*pFailed)[(size_t)i] = std::string("Sample failed to load: ") + afx_status_str(Batch.mStatus[(size_t)i]);
+  }
+  return Results;
+}
+
 }  // namespace
 
 std::vector<TSampleDescriptors> TSampleAnalyser::AnalyzeLowLevelDescriptors(
@@ -155,10 +198,9 @@ std::vector<TSampleDescriptors> TSampleAnalyser::AnalyzeLowLevelDescriptors(
   std::vector<afx_buf> Buffers((size_t)n);
   for (int32_t i = 0; i < n; ++i) Buffers[i] = {Samples[i]->data(), AFX_PCM_F64, 0, (int64_t)Samples[i]->size()};
   TBatchGuard Batch;
-  int Status = afx_batch_create(mpPlan, Buffers.data(), n, kEverything, &Batch.mpBatch);
-  if (Status == AFX_OK) Status = afx_batch_run(Batch.mpBatch);
+  const int Status = afx_batch_create(mpPlan, Buffers.data(), n, kEverything, &Batch.mpBatch);
   if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
-  return Collect(Batch, n, pFailed);
+  return RunAndCollect(Batch.mpBatch, n, nullptr, {}, mSampleRate, pFailed);
 }
 
 // LoadSample (SampleAnalyser.cpp:443-719, after the container decode) + AnalyzeLowLevelDescriptors +
@@ -167,143 +209,14 @@ std::vector<TSampleDescriptors> TSampleAnalyser::AnalyzeLowLevelDescriptors(
 std::vector<TSampleDescriptors> TSampleAnalyser::Analyze(const std::vector<TDecodedSample>& Files,
                                                          std::vector<TSampleDataInfo>* pInfo,
                                                          std::vector<std::string>* pFailed) const {
-  const int32_t n = (int32_t)Files.size();
-  std::vector<afx_raw> Raws((size_t)n);
-  for (int32_t i = 0; i < n; ++i)
-    Raws[i] = {Files[i].mpInterleavedSamples, Files[i].mFormat, Files[i].mNumberOfChannels, Files[i].mSampleRate, 0,
-               Files[i].mNumberOfSampleFrames};
-  std::vector<afx_load_info> Info((size_t)n);
   TBatchGuard Batch;
-  int Status = afx_batch_create_from_raw(mpPlan, Raws.data(), n, kEverything, &Batch.mpBatch, Info.data());
-  if (Status == AFX_OK) Status = SetFileInfo(Batch.mpBatch, Files, Info, mSampleRate);
-  if (Status == AFX_OK) Status = afx_batch_run(Batch.mpBatch);
-  if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
-  if (pInfo) {
-    pInfo->resize((size_t)n);
-    for (int32_t i = 0; i < n; ++i)
-      (*pInfo)[i] = {Info[i].peak_value, Info[i].rms_value, Info[i].data_offset, Info[i].n_samples};
-  }
-  return Collect(Batch, n, pFailed);
-}
-
-namespace {
-std::vector<TSampleDescriptors> Collect(TBatchGuard& Batch, int32_t n, std::vector<std::string>* pFailed) {
-  int Status = AFX_OK;
-  const size_t F = (size_t)afx_batch_total_frames(Batch.mpBatch);
-
-  // host arrays for every series: [F][W] values and [n][W][13] statistics
-  std::vector<std::vector<double>> Values, Stats;
-  afx_out Out = {};
-  afx_stats_out StatsOut = {};
-  auto Bind = [&](double* afx_out::*pOut, double* afx_stats_out::*pStat, int W) {
-    Values.emplace_back(F * (size_t)W);
-    Stats.emplace_back((size_t)n * (size_t)W * AFX_NUM_STATISTICS);
-    Out.*pOut = Values.back().data();
-    StatsOut.*pStat = Stats.back().data();
-  };
-  for (const TScalarSeries& S : kScalarSeries) Bind(S.mpOut, S.mpStat, 1);
-  for (const TVectorSeries<14>& S : kSubBandSeries) Bind(S.mpOut, S.mpStat, 14);
-  for (const TVectorSeries<28>& S : kBandSeries) Bind(S.mpOut, S.mpStat, 28);
-  std::vector<int64_t> Offset((size_t)n + 1);
-  std::vector<int32_t> BufStatus((size_t)n), StatsStatus((size_t)n);
-  std::vector<double> EffectiveLength((size_t)n * 3);
-  Out.effective_length = EffectiveLength.data();
-  Out.frame_offset = Offset.data();
-  Out.buf_status = BufStatus.data();
-  StatsOut.stats_status = StatsStatus.data();
-  Status = afx_batch_fetch(Batch.mpBatch, &Out);
-  if (Status == AFX_OK) Status = afx_batch_fetch_statistics(Batch.mpBatch, &StatsOut);
-  std::vector<int64_t> RhythmOffset((size_t)n + 1);
-  const size_t RhythmRows = (size_t)afx_batch_rhythm_frames(Batch.mpBatch, RhythmOffset.data());
-  std::vector<double> Onsets(RhythmRows * 2), RhythmScalars((size_t)n * AFX_NUM_RHYTHM_SCALARS),
-      RhythmStatistics((size_t)n * 2 * AFX_NUM_STATISTICS);
-  if (Status == AFX_OK) Status = afx_batch_fetch_rhythm(Batch.mpBatch, Onsets.data(), RhythmScalars.data(), RhythmStatistics.data());
-  if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
-
-  std::vector<TSampleDescriptors> Results((size_t)n);
-  if (pFailed) pFailed->assign((size_t)n, std::string());
-  for (int32_t i = 0; i < n; ++i) {
-    const int32_t Bad = (BufStatus[i] != AFX_OK) ? BufStatus[i] : StatsStatus[i];
-    if (Bad != AFX_OK) {
-      if (pFailed) (*pFailed)[i] = std::string("Sample failed to load: ") + afx_status_str(Bad);
-      continue;
-    }
-    const int64_t f0 = Offset[i], nf = Offset[i + 1] - Offset[i];
-    TSampleDescriptors& R = Results[i];
-    R.mEffectiveLength48dB = EffectiveLength[(size_t)i * 3];
-    R.mEffectiveLength24dB = EffectiveLength[(size_t)i * 3 + 1];
-    R.mEffectiveLength12dB = EffectiveLength[(size_t)i * 3 + 2];
-    for (const TScalarSeries& S : kScalarSeries) {
-      Fill(R.*(S.mpDst), (Out.*(S.mpOut)) + f0, nf);
-      FillStatistics(R.*(S.mpDst), (StatsOut.*(S.mpStat)) + (size_t)i * AFX_NUM_STATISTICS);
-    }
-    for (const TVectorSeries<14>& S : kSubBandSeries) {
-      Fill(R.*(S.mpDst), (Out.*(S.mpOut)) + f0 * 14, nf);
-      FillStatistics(R.*(S.mpDst), (StatsOut.*(S.mpStat)) + (size_t)i * 14 * AFX_NUM_STATISTICS);
-    }
-    for (const TVectorSeries<28>& S : kBandSeries) {
-      Fill(R.*(S.mpDst), (Out.*(S.mpOut)) + f0 * 28, nf);
-      FillStatistics(R.*(S.mpDst), (StatsOut.*(S.mpStat)) + (size_t)i * 28 * AFX_NUM_STATISTICS);
-    }
-    FillRhythm(R, i, RhythmOffset.data(), Onsets.data(), RhythmScalars.data(), RhythmStatistics.data());
-  }
+  std::vector<afx_load_info> Info;
+  CreateFromFiles(mpPlan, Files, Batch, Info);
+  std::vector<TSampleDescriptors> Results = RunAndCollect(Batch.mpBatch, (int32_t)Files.size(), &Files, Info, mSampleRate, pFailed);
+  if (pInfo) *pInfo = InfoOf(Info);
   return Results;
 }
-}  // namespace
 
-namespace {
-// the series of afx_batch_record_layout, in its order
-double* afx_out::* const kRecordOrder[AFX_NUM_SERIES] = {
-    &afx_out::mfcc, &afx_out::spectral_rms, &afx_out::spectral_centroid, &afx_out::spectral_spread, &afx_out::spectral_skewness,
-    &afx_out::spectral_kurtosis, &afx_out::spectral_rolloff, &afx_out::spectral_flatness, &afx_out::spectral_flux,
-    &afx_out::spectrum_bands, &afx_out::amplitude_peak, &afx_out::amplitude_rms, &afx_out::sub_rms, &afx_out::sub_flatness,
-    &afx_out::sub_flux, &afx_out::sub_complexity, &afx_out::sub_contrast, &afx_out::spectral_contrast,
-    &afx_out::amplitude_silence, &afx_out::amplitude_envelope, &afx_out::spectral_complexity, &afx_out::auto_correlation,
-    &afx_out::f0, &afx_out::f0_confidence, &afx_out::failsafe_f0, &afx_out::spectral_inharmonicity, &afx_out::tristimulus1,
-    &afx_out::tristimulus2, &afx_out::tristimulus3};
-int SeriesIndex(double* afx_out::*pMember) {
-  for (int i = 0; i < AFX_NUM_SERIES; ++i)
-    if (kRecordOrder[i] == pMember) return i;
-  return -1;
-}
-void FillStrided(TFramedScalarData& Dst, const double* pSrc, int64_t Frames, int Stride) {
-  Dst.mValues.resize((size_t)Frames);
-  for (int64_t f = 0; f < Frames; ++f) Dst.mValues[(size_t)f] = pSrc[f * Stride];
-}
-template <int W>
-void FillStrided(TFramedVectorData<W>& Dst, const double* pSrc, int64_t Frames, int Stride) {
-  Dst.mValues.resize((size_t)Frames);
-  for (int64_t f = 0; f < Frames; ++f)
-    for (int b = 0; b < W; ++b) Dst.mValues[(size_t)f][b] = pSrc[f * Stride + b];
-}
-}  // namespace
-
-TSampleDescriptors TRecordBatch::Descriptors(int i) const {
-  TSampleDescriptors R;
-  const int64_t f0 = mFrameOffset[(size_t)i], nf = mFrameOffset[(size_t)i + 1] - f0;
-  R.mEffectiveLength48dB = mEffectiveLength[(size_t)i * 3];
-  R.mEffectiveLength24dB = mEffectiveLength[(size_t)i * 3 + 1];
-  R.mEffectiveLength12dB = mEffectiveLength[(size_t)i * 3 + 2];
-  const double* const pRows = mpRecords + f0 * mStride;
-  const double* const pStats = mpStatistics + (size_t)i * mStride * AFX_NUM_STATISTICS;
-  auto Each = [&](auto& Series) {
-    for (const auto& S : Series) {
-      const int k = SeriesIndex(S.mpOut);
-      if (k < 0 || mOffsets[k] < 0) continue;
-      FillStrided(R.*(S.mpDst), pRows + mOffsets[k], nf, mStride);
-      FillStatistics(R.*(S.mpDst), pStats + (size_t)mOffsets[k] * AFX_NUM_STATISTICS);
-    }
-  };
-  Each(kScalarSeries);
-  Each(kSubBandSeries);
-  Each(kBandSeries);
-  if (!mRhythmOffset.empty() && mpRhythmScalars)
-    FillRhythm(R, i, mRhythmOffset.data(), mpRhythmOnsets, mpRhythmScalars, mpRhythmStatistics);
-  return R;
-}
-
-// onsets [rows][2] + scalars [n][14] + onset statistics [n][2][13]; LoadSample pads a file by at most one 2048-sample
-// frame, so it has at most samples / 128 + 17 rows
 // sample frames of a file once it is at `Rate` (NewSizeInSamples, SampleAnalyser.cpp:572-573)
 int64_t TSampleAnalyser::ConvertedSampleFrames(const TDecodedSample& File, int Rate) {
   if (File.mSampleRate <= 0 || File.mSampleRate == Rate) return File.mNumberOfSampleFrames;
@@ -316,54 +229,25 @@ bool TSampleAnalyser::DeviceUsable() const {
   return Status == AFX_OK || Status == AFX_ERR_OUT_OF_MEMORY;
 }
 
+// LoadSample pads a file by at most one 2048-sample frame, so it has at most samples / 128 + 17 rows of onsets
 size_t TSampleAnalyser::RhythmDoubles(const std::vector<TDecodedSample>& Files) const {
   size_t Rows = 0;
   for (const TDecodedSample& f : Files) Rows += (size_t)(ConvertedSampleFrames(f, mSampleRate) / 128) + 17;
-  return Rows * 2 + Files.size() * (AFX_NUM_RHYTHM_SCALARS + 2 * AFX_NUM_STATISTICS);
+  return Rows * 2 + Files.size() * kRhythmDoublesPerFile;
 }
 
 bool TSampleAnalyser::AnalyzeToRecords(const std::vector<TDecodedSample>& Files, double* pRecords, size_t RecordCapacity,
                                        double* pStatistics, double* pRhythm, size_t RhythmCapacity, TRecordBatch& Result) const {
-  const int32_t n = (int32_t)Files.size();
-  std::vector<afx_raw> Raws((size_t)n);
-  for (int32_t i = 0; i < n; ++i)
-    Raws[i] = {Files[i].mpInterleavedSamples, Files[i].mFormat, Files[i].mNumberOfChannels, Files[i].mSampleRate, 0,
-               Files[i].mNumberOfSampleFrames};
-  std::vector<afx_load_info> Info((size_t)n);
   TBatchGuard Batch;
-  auto Now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  std::vector<afx_load_info> Info;
   const double t0 = Now();
-  int Status = afx_batch_create_from_raw(mpPlan, Raws.data(), n, kEverything, &Batch.mpBatch, Info.data());
-  if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
+  CreateFromFiles(mpPlan, Files, Batch, Info);
   const double t1 = Now();
-  Result = TRecordBatch();
-  afx_batch_record_layout(Batch.mpBatch, &Result.mStride, Result.mOffsets, Result.mWidths);
-  const size_t Frames = (size_t)afx_batch_total_frames(Batch.mpBatch);
+  const TResultDoubles Doubles = Layout(Batch.mpBatch, (int32_t)Files.size(), Result);
   if (Result.mStride > kMaxStride) throw TReadableException("AnalyzeToRecords: record stride exceeds kMaxStride");   // larger buffers would not help
-  if (Frames * (size_t)Result.mStride > RecordCapacity) return false;
-  Result.mRhythmOffset.resize((size_t)n + 1);
-  const size_t RhythmRows = (size_t)afx_batch_rhythm_frames(Batch.mpBatch, Result.mRhythmOffset.data());
-  if (RhythmRows * 2 + (size_t)n * (AFX_NUM_RHYTHM_SCALARS + 2 * AFX_NUM_STATISTICS) > RhythmCapacity) return false;
-  Status = SetFileInfo(Batch.mpBatch, Files, Info, mSampleRate);
-  if (Status == AFX_OK) Status = afx_batch_run(Batch.mpBatch);
-  const double t2 = Now();
-  Result.mFrameOffset.resize((size_t)n + 1);
-  Result.mStatus.resize((size_t)n);
-  Result.mEffectiveLength.resize((size_t)n * 3);
-  if (Status == AFX_OK)
-    Status = afx_batch_fetch_records(Batch.mpBatch, pRecords, pStatistics, Result.mFrameOffset.data(), Result.mStatus.data(),
-                                     Result.mEffectiveLength.data());
-  double* const pOnsets = pRhythm;
-  double* const pScalars = pOnsets + RhythmRows * 2;
-  double* const pOnsetStatistics = pScalars + (size_t)n * AFX_NUM_RHYTHM_SCALARS;
-  if (Status == AFX_OK) Status = afx_batch_fetch_rhythm(Batch.mpBatch, pOnsets, pScalars, pOnsetStatistics);
-  Result.mpRhythmOnsets = pOnsets; Result.mpRhythmScalars = pScalars; Result.mpRhythmStatistics = pOnsetStatistics;
-  if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
-  Result.mSeconds[0] = t1 - t0; Result.mSeconds[1] = t2 - t1; Result.mSeconds[2] = Now() - t2;
-  Result.mpRecords = pRecords;
-  Result.mpStatistics = pStatistics;
-  Result.mInfo.resize((size_t)n);
-  for (int32_t i = 0; i < n; ++i) Result.mInfo[i] = {Info[i].peak_value, Info[i].rms_value, Info[i].data_offset, Info[i].n_samples};
+  if (Doubles.mRecords > RecordCapacity || Doubles.mRhythm > RhythmCapacity) return false;
+  RunAndFetch(Batch.mpBatch, (int32_t)Files.size(), &Files, Info, mSampleRate, pRecords, pStatistics, pRhythm, Result);
+  Result.mSeconds[0] = t1 - t0;
   return true;
 }
 

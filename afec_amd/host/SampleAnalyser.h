@@ -14,7 +14,7 @@
 #include <string>
 #include <vector>
 
-struct afx_plan;
+#include "../../include/afx.h"
 
 namespace afec {
 
@@ -92,7 +92,7 @@ struct TSampleDataInfo {
 // keeps the transfers direct); Descriptors(i) materialises file i the way TSampleAnalyser::Analyze returns it.
 struct TRecordBatch {
   int mStride = 0;
-  int mOffsets[32] = {}, mWidths[32] = {};          // per series, afx_batch_record_layout
+  int mOffsets[AFX_NUM_SERIES] = {}, mWidths[AFX_NUM_SERIES] = {};   // per series, afx_batch_record_layout
   const double* mpRecords = nullptr;                // [frames][stride]
   const double* mpStatistics = nullptr;             // [files][stride][13]
   std::vector<int64_t> mFrameOffset;                // [files + 1]
@@ -146,9 +146,10 @@ public:
   // RhythmCapacity doubles (RhythmDoubles() of the files is always enough).  Returns false (and leaves Batch empty)
   // when the records do not fit RecordCapacity or the rhythm results RhythmCapacity: call again with larger buffers.
   enum {
-    kMaxStride = 134,                                 // columns of a per-frame record at most (TRecordBatch::mStride)
-    kStatisticsPerSeries = 13,                        // TStatistics::Calc's values per column (AFX_NUM_STATISTICS)
-    kRhythmScalars = 14,                              // TRecordBatch::mpRhythmScalars per file (AFX_NUM_RHYTHM_SCALARS)
+    kMaxStride = 134,                                 // columns of a per-frame record at most (TRecordBatch::mStride):
+                                                      // every series' width, added up and checked in DescriptorTable.h
+    kStatisticsPerSeries = AFX_NUM_STATISTICS,        // TStatistics::Calc's values per column
+    kRhythmScalars = AFX_NUM_RHYTHM_SCALARS,          // TRecordBatch::mpRhythmScalars per file
     kRhythmStatistics = 2 * kStatisticsPerSeries,     // TRecordBatch::mpRhythmStatistics per file: the two onset series'
     kRhythmDoublesPerFile = kRhythmScalars + kRhythmStatistics   // what a file adds to the rhythm buffer besides its onset rows
   };
