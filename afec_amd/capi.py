@@ -49,6 +49,18 @@ D_SPECTRAL_STATS = 0x1FE
 D_ALL_LOW_LEVEL = 0x1FFF
 D_NEIGHBOURS = 0x3F8000
 D_ALL_PER_FRAME = D_ALL_LOW_LEVEL | D_NEIGHBOURS
+# afx_batch_fetch_high_level: the bits a batch's mask must hold, the scalars' order (AFX_HL_*), the signature's shape
+D_HIGH_LEVEL_INPUTS = (D_AMPLITUDE_SILENCE | D_AMPLITUDE_PEAK | D_F0 | D_AUTO_CORRELATION | D_SPECTRAL_ROLLOFF |
+                       D_SPECTRAL_CENTROID | D_SPECTRAL_FLATNESS | D_SPECTRAL_FLUX | D_SPECTRAL_COMPLEXITY |
+                       D_SPECTRAL_INHARMONICITY | D_BAND_FEATURES | D_SPECTRUM_BANDS | D_RHYTHM)
+HL_SCALARS = ["peak_db", "rms_db", "base_note", "base_note_confidence", "bpm", "bpm_confidence", "brightness", "noisiness",
+              "harmonicity", "spectral_flatness", "spectral_flux", "spectral_complexity", "spectral_contrast",
+              "spectral_inharmonicity", "pitch_confidence"]
+(HL_PEAK_DB, HL_RMS_DB, HL_BASE_NOTE, HL_BASE_NOTE_CONFIDENCE, HL_BPM, HL_BPM_CONFIDENCE, HL_BRIGHTNESS, HL_NOISINESS,
+ HL_HARMONICITY, HL_SPECTRAL_FLATNESS, HL_SPECTRAL_FLUX, HL_SPECTRAL_COMPLEXITY, HL_SPECTRAL_CONTRAST,
+ HL_SPECTRAL_INHARMONICITY, HL_PITCH_CONFIDENCE) = range(15)
+NUM_HL_SCALARS = len(HL_SCALARS)
+HL_SIGNATURE_FRAMES, HL_SIGNATURE_BANDS = 64, 14
 PRECISION_F64, PRECISION_F32 = 0, 1
 PCM_F32, PCM_F64 = 0, 1
 FRAME_KERNEL_AUTO, FRAME_KERNEL_WAVE64, FRAME_KERNEL_HALFWAVE = 0, 1, 2   # afx_plan_desc.frame_kernel
@@ -64,6 +76,7 @@ EXPORTS = [
     "afx_host_alloc", "afx_host_free", "afx_batch_record_layout", "afx_batch_fetch_records",
     "afx_batch_set_file_info", "afx_batch_rhythm_frames", "afx_batch_fetch_rhythm", "afx_batch_fetch_onset_functions",
     "afx_plan_set_blocking_wait", "afx_batch_get_info", "afx_plan_probe_device", "afx_device_count",
+    "afx_batch_fetch_high_level",
 ]
 RAW_I16, RAW_I24, RAW_F32, RAW_I32, RAW_F64 = 0, 1, 2, 3, 4
 
@@ -133,6 +146,10 @@ class _LoadInfo(ctypes.Structure):
     _fields_ = [("peak_value", ctypes.c_float), ("rms_value", ctypes.c_float), ("data_offset", ctypes.c_int32),
                 ("silent_leading", ctypes.c_int32), ("silent_trailing", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("n_samples", ctypes.c_int64)]
+
+
+class _HighOut(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("scalars", "signature", "pitch", "peak", "status")]
 
 
 class _StatsOut(ctypes.Structure):
@@ -219,6 +236,7 @@ def load_library():
     L.afx_batch_fetch_onset_functions.argtypes = [vp, vp]
     L.afx_algorithmic_bytes_per_frame.restype = i64
     L.afx_algorithmic_bytes_per_frame.argtypes = [vp, u32, i32]
+    L.afx_batch_fetch_high_level.argtypes = [vp, ctypes.POINTER(_LoadInfo), ctypes.POINTER(_HighOut)]
     _lib = L
     return L
 
@@ -464,6 +482,28 @@ class Batch:
             odf = np.zeros((max(rows, 1), 2), dtype=np.float32)
             _check(self.L, self.L.afx_batch_fetch_onset_functions(self.h, odf.ctypes.data))
             res["onset_functions"] = odf[:rows]
+        return res
+
+    def fetch_high_level(self, levels=None, want=("scalars", "signature", "pitch", "peak", "status")):
+        """afx_batch_fetch_high_level: the model-free high-level descriptors of every buffer (SampleAnalyser.cpp:1234-1606).
+        levels: the load-info dicts Plan.batch_from_raw returned (their peak_value / rms_value become peak_db / rms_db;
+        None: the two are NaN).  dict: "scalars" [n_bufs][15] (HL_SCALARS order), "signature" [n_bufs][64][14], "pitch" [F],
+        "peak" [F], "status" [n_bufs]; `want` names the members to fetch (the others are passed as NULL)."""
+        n = self.n_bufs
+        res = {"scalars": np.zeros((n, NUM_HL_SCALARS)), "signature": np.zeros((n, HL_SIGNATURE_FRAMES, HL_SIGNATURE_BANDS)),
+               "pitch": np.zeros(self.total_frames), "peak": np.zeros(self.total_frames), "status": np.zeros(n, dtype=np.int32)}
+        res = {k: v for k, v in res.items() if k in want}
+        out = _HighOut()
+        for k, v in res.items():
+            setattr(out, k, v.ctypes.data if v.size else None)
+        info = None
+        if levels is not None:
+            if len(levels) != n:
+                raise ValueError("levels must hold one load info per buffer")
+            info = (_LoadInfo * max(1, n))()
+            for i, d in enumerate(levels):
+                info[i].peak_value, info[i].rms_value = d["peak_value"], d["rms_value"]
+        _check(self.L, self.L.afx_batch_fetch_high_level(self.h, info, ctypes.byref(out)))
         return res
 
     def close(self):

@@ -11,6 +11,8 @@
 //                       afx_extract_batch
 //   afx_batch_run.cpp   afx_batch_run: the kernels of one pass in stream order (SampleAnalyser.cpp:814-1048)
 //   afx_batch_fetch.cpp results back to the host, batch information, afx_batch_destroy
+//   afx_high_level.cpp  afx_batch_fetch_high_level (SampleAnalyser.cpp:1234-1606); its launcher is declared in
+//                       highlevel/afx_highlevel.h, and none of the files above refers to either
 //
 // Nothing here computes a descriptor: every kernel lives in the .hip files (afx_internal.h declares their launchers).
 #pragma once
@@ -134,6 +136,9 @@ struct Workspace {
   Buf rt_odf, rt_onsets, rt_scratch, rt_scalars, rt_stats, rt_polar;   // rhythm tracker (its host-filled tables lie in `tables`)
   Buf stat_tmp;                                                                 // half-wave statistics class
   Buf rs_files, rs_groups, rs_ngroups;                                          // sample-rate conversion (afx_resample.hip)
+  Buf high;                                                                     // afx_batch_fetch_high_level's result block (afx_high_level.cpp)
+  void* h_high = nullptr;         // ... and the page-locked host block it lands in (with the peak / rms pairs on their way up)
+  size_t h_high_cap = 0;
   std::vector<Buf*> all_bufs();   // every Buf member above, each exactly once: ws_free and bytes() walk this list
   size_t bytes();
 };

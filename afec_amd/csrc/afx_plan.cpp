@@ -355,7 +355,7 @@ const char* afx_build_info(void) {
 #ifndef AFX_SRC_HASH
 #define AFX_SRC_HASH "unknown"
 #endif
-  return "afx abi=" "6" " arch=gfx950 stamps=" AFX_INFO_STAMPS " ablation=" AFX_INFO_ABL " src=" AFX_SRC_HASH;
+  return "afx abi=" "7" " arch=gfx950 stamps=" AFX_INFO_STAMPS " ablation=" AFX_INFO_ABL " src=" AFX_SRC_HASH;
 }
 
 int afx_plan_create(const afx_plan_desc* desc, afx_plan** out_plan) {

@@ -16,7 +16,7 @@ namespace host {
 
 std::vector<Workspace::Buf*> Workspace::all_bufs() {
   return {&tables, &pcm, &rec, &mag, &stats, &follower, &efflen, &raw, &files, &scan, &partial, &place, &queue, &rt_polar, &rt_odf,
-          &rt_onsets, &rt_scratch, &rt_scalars, &rt_stats, &stat_tmp, &rs_files, &rs_groups, &rs_ngroups};
+          &rt_onsets, &rt_scratch, &rt_scalars, &rt_stats, &stat_tmp, &rs_files, &rs_groups, &rs_ngroups, &high};
 }
 size_t Workspace::bytes() {
   size_t n = 0;
@@ -28,6 +28,7 @@ void ws_free(Workspace* w) {
   if (!w) return;
   for (Workspace::Buf* b : w->all_bufs()) hipFree(b->p);
   if (w->h_pin) hipHostFree(w->h_pin);
+  if (w->h_high) hipHostFree(w->h_high);
   if (w->ev0) hipEventDestroy(w->ev0);
   if (w->ev1) hipEventDestroy(w->ev1);
   if (w->ev_fork) hipEventDestroy(w->ev_fork);

@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define AFX_VERSION 6
+#define AFX_VERSION 7
 
 /* ---- status codes (replace TReadableException on this path, SampleAnalyser.cpp:397-408) ---- */
 enum {
@@ -376,6 +376,59 @@ int64_t afx_batch_rhythm_frames(const afx_batch* batch, int64_t* offsets /* [n_b
 int afx_batch_fetch_rhythm(afx_batch* batch, double* onsets, double* scalars, double* onset_statistics);
 /* the onset functions before median removal, float [total][2]: for the parity tests */
 int afx_batch_fetch_onset_functions(afx_batch* batch, float* odf);
+
+/* ---- high-level descriptors (ABI 7): the model-free part of TSampleAnalyser::AnalyzeHighLevelDescriptors,
+ * SampleAnalyser.cpp:1234-1606 ---- *
+ * What the reference's default run (--level high) reduces the low-level series to, computed on the GPU from what a batch
+ * holds in device memory after afx_batch_run (one kernel, one transfer of about 1 000 doubles per file); no mask bit of
+ * its own, nothing added to what afx_batch_run launches.  The classes, categories and their signatures (the two
+ * classification models, :1075-1231) are not part of it.
+ *   audible frames     those with amplitude_silence == 0 (:865-868, 420-440)
+ *   base note          the pitch-confidence class (f0_confidence above 0.8 / 0.5 / 0.2, 20 Hz < f0 < rate / 4) is chosen
+ *                      by the mean f0 confidence of the audible frames (:1236-1277); the confident pitches of ALL frames
+ *                      (:1279-1292), their TStatistics::Median (the element of rank (n-1)/2, Statistics.cpp:316-413) as a
+ *                      MIDI note (aubio_freqtomidi), -1 when there is none or it is outside 20 Hz .. rate / 4 (:1294-1303)
+ *   .. confidence      that mean x (1 - min(1, standard deviation of the notes' distances to the base note / 6)), 0 without
+ *                      a base note (:1306-1331)
+ *   peak_db, rms_db    TAudioMath::LinToDb (the float overload, AudioMath.inl:38-53) of TSampleData::mPeakValue / mRmsValue
+ *                      (:1336-1339).  A batch does not keep the two: the caller passes the afx_load_info array that
+ *                      afx_batch_create_from_raw filled; with levels == NULL both scalars are NaN
+ *   bpm                rhythm_final_tempo quantised to 0.5 (TMath::Quantize, kRoundToNearest, InlineMath.inl:625-636),
+ *                      its confidence unchanged (:1345-1349)
+ *   brightness, noisiness, harmonicity   :1354-1444; spectral_* the means over the audible frames, 0 without one
+ *                      (:1529-1553); pitch_confidence the mean f0 confidence of the audible frames (:1601)
+ *   signature          frequency_bands merged to 14 (sSpectrumBands), pow(1.25 v, 1/6), resampled to 64 positions by
+ *                      SInterpolateCubic with the neighbours clamped as written, the position truncated (:1450-1520)
+ *   pitch              per frame: the f0 of the last confident audible frame at or before it, before the first one the
+ *                      first one's if it lies in frames 0 .. max(1, F/4) and 0 otherwise, each as aubio_freqtomidi
+ *                      (0 below 2 Hz; :1557-1596)
+ *   peak               amplitude_peak (:1606)
+ * A buffer without frames (empty, or refused: buf_status) gets zeros -- the reference's resampling loop is undefined for
+ * it.  Sums are formed in another order than the reference's serial TStatistics::Sum; a file whose mean f0 confidence
+ * lies within rounding of 0.8 or 0.5 may therefore fall into the neighbouring class. */
+#define AFX_HL_SIGNATURE_FRAMES 64 /* kNumberOfHighLevelSpectrumBandFrames, SampleDescriptors.h */
+#define AFX_HL_SIGNATURE_BANDS 14  /* kNumberOfHighLevelSpectrumBands                           */
+#define AFX_NUM_HL_SCALARS 15
+enum {
+  AFX_HL_PEAK_DB = 0, AFX_HL_RMS_DB, AFX_HL_BASE_NOTE, AFX_HL_BASE_NOTE_CONFIDENCE, AFX_HL_BPM, AFX_HL_BPM_CONFIDENCE,
+  AFX_HL_BRIGHTNESS, AFX_HL_NOISINESS, AFX_HL_HARMONICITY, AFX_HL_SPECTRAL_FLATNESS, AFX_HL_SPECTRAL_FLUX,
+  AFX_HL_SPECTRAL_COMPLEXITY, AFX_HL_SPECTRAL_CONTRAST, AFX_HL_SPECTRAL_INHARMONICITY, AFX_HL_PITCH_CONFIDENCE
+};
+/* the bits a batch's mask must hold for the fetch (all of them; AFX_D_BAND_FEATURES for spectral_contrast) */
+#define AFX_D_HIGH_LEVEL_INPUTS                                                                                          \
+  (AFX_D_AMPLITUDE_SILENCE | AFX_D_AMPLITUDE_PEAK | AFX_D_F0 | AFX_D_AUTO_CORRELATION | AFX_D_SPECTRAL_ROLLOFF |         \
+   AFX_D_SPECTRAL_CENTROID | AFX_D_SPECTRAL_FLATNESS | AFX_D_SPECTRAL_FLUX | AFX_D_SPECTRAL_COMPLEXITY |                 \
+   AFX_D_SPECTRAL_INHARMONICITY | AFX_D_BAND_FEATURES | AFX_D_SPECTRUM_BANDS | AFX_D_RHYTHM)
+typedef struct {
+  double* scalars;   /* [n_bufs][AFX_NUM_HL_SCALARS], AFX_HL_* order                                  */
+  double* signature; /* [n_bufs][64][14]  mHighLevelSpectrumSignature                                 */
+  double* pitch;     /* [F] MIDI notes, rows as afx_out (mHighLevelPitch)                             */
+  double* peak;      /* [F] mHighLevelPeak, rows as afx_out                                           */
+  int32_t* status;   /* [n_bufs], optional: repeats buf_status                                        */
+} afx_high_out;      /* any pointer may be NULL */
+/* After afx_batch_run (before the first run: AFX_ERR_INVALID_ARG, as the other fetches answer), any number of times;
+ * AFX_ERR_INVALID_ARG when the batch's mask lacks one of AFX_D_HIGH_LEVEL_INPUTS.  Synchronous. */
+int afx_batch_fetch_high_level(afx_batch* batch, const afx_load_info* levels /* [n_bufs] or NULL */, afx_high_out* out);
 
 /* Page-locked host memory for PCM and result arrays: transfers from / to such buffers run at the
  * host link's rate (pageable memory is staged by the runtime at a fraction of it). */
