@@ -61,6 +61,11 @@ HL_SCALARS = ["peak_db", "rms_db", "base_note", "base_note_confidence", "bpm", "
  HL_SPECTRAL_INHARMONICITY, HL_PITCH_CONFIDENCE) = range(15)
 NUM_HL_SCALARS = len(HL_SCALARS)
 HL_SIGNATURE_FRAMES, HL_SIGNATURE_BANDS = 64, 14
+# afx_batch_fetch_classification_features: the bits a batch's mask must hold, the vector's shape
+D_CLASSIFICATION_INPUTS = (D_MFCC | D_SPECTRAL_RMS | D_SPECTRAL_FLATNESS | D_SPECTRAL_FLUX | D_SPECTRUM_BANDS |
+                           D_BAND_FEATURES | D_AMPLITUDE_RMS | D_AMPLITUDE_SILENCE | D_SPECTRAL_COMPLEXITY | D_F0 |
+                           D_STATISTICS | D_EFFECTIVE_LENGTH | D_RHYTHM)
+CF_TIME_FRAMES, NUM_CLASSIFICATION_FEATURES, NUM_CF_SILENCE = 48, 1680, 21
 PRECISION_F64, PRECISION_F32 = 0, 1
 PCM_F32, PCM_F64 = 0, 1
 FRAME_KERNEL_AUTO, FRAME_KERNEL_WAVE64, FRAME_KERNEL_HALFWAVE = 0, 1, 2   # afx_plan_desc.frame_kernel
@@ -77,6 +82,7 @@ EXPORTS = [
     "afx_batch_set_file_info", "afx_batch_rhythm_frames", "afx_batch_fetch_rhythm", "afx_batch_fetch_onset_functions",
     "afx_plan_set_blocking_wait", "afx_batch_get_info", "afx_plan_probe_device", "afx_device_count",
     "afx_batch_fetch_high_level",
+    "afx_batch_fetch_classification_features", "afx_classification_feature_name", "afx_plan_get_silence_features",
 ]
 RAW_I16, RAW_I24, RAW_F32, RAW_I32, RAW_F64 = 0, 1, 2, 3, 4
 
@@ -237,8 +243,24 @@ def load_library():
     L.afx_algorithmic_bytes_per_frame.restype = i64
     L.afx_algorithmic_bytes_per_frame.argtypes = [vp, u32, i32]
     L.afx_batch_fetch_high_level.argtypes = [vp, ctypes.POINTER(_LoadInfo), ctypes.POINTER(_HighOut)]
+    L.afx_batch_fetch_classification_features.argtypes = [vp, vp, vp, vp]
+    L.afx_classification_feature_name.argtypes = [i32, ctypes.c_char_p, i32]
+    L.afx_plan_get_silence_features.argtypes = [vp, vp]
     _lib = L
     return L
+
+
+def classification_feature_names():
+    """the 1 680 names of afx_batch_fetch_classification_features' columns (afx_classification_feature_name; no device)"""
+    L = load_library()
+    buf = ctypes.create_string_buffer(64)
+    names = []
+    for i in range(NUM_CLASSIFICATION_FEATURES):
+        n = L.afx_classification_feature_name(i, buf, len(buf))
+        if n < 0:
+            _check(L, n)
+        names.append(buf.value.decode())
+    return names
 
 
 def pinned_array(shape, dtype):
@@ -341,6 +363,13 @@ class Plan:
         f, c = ctypes.c_int32(), ctypes.c_int32()
         _check(self.L, self.L.afx_plan_get_bin_range(self.h, ctypes.byref(f), ctypes.byref(c)))
         return f.value, c.value
+
+    def silence_features(self):
+        """afx_plan_get_silence_features: [21] what a time position without a frame is filled with (frequency_bands 0..13,
+        spectral_rms, _flatness, _flux, _contrast, _complexity, f0_confidence, amplitude_rms of one frame of zeros)"""
+        a = np.zeros(NUM_CF_SILENCE)
+        _check(self.L, self.L.afx_plan_get_silence_features(self.h, a.ctypes.data))
+        return a
 
     def num_frames(self, n_samples):
         return int(self.L.afx_num_frames(self.h, int(n_samples)))
@@ -505,6 +534,17 @@ class Batch:
                 info[i].peak_value, info[i].rms_value = d["peak_value"], d["rms_value"]
         _check(self.L, self.L.afx_batch_fetch_high_level(self.h, info, ctypes.byref(out)))
         return res
+
+    def fetch_classification_features(self):
+        """afx_batch_fetch_classification_features: the reference's model input of every buffer
+        (SampleClassificationDescriptors.cpp:395-561) -> (features [n_bufs][1680], non_finite [n_bufs], status [n_bufs]);
+        classification_feature_names() names the columns."""
+        n = self.n_bufs
+        features = np.zeros((max(1, n), NUM_CLASSIFICATION_FEATURES))   # one spare row: the C call wants a pointer for n = 0 too
+        non_finite, status = np.zeros(max(1, n), dtype=np.int32), np.zeros(max(1, n), dtype=np.int32)
+        _check(self.L, self.L.afx_batch_fetch_classification_features(self.h, features.ctypes.data, non_finite.ctypes.data,
+                                                                      status.ctypes.data))
+        return features[:n], non_finite[:n], status[:n]
 
     def close(self):
         if getattr(self, "h", None):

@@ -9,6 +9,30 @@
 
 using namespace afx::host;
 
+namespace afx {
+namespace host {
+
+int effective_length_seconds(afx_batch* b, double* seconds) {
+  if (!b->d_efflen) return fail(AFX_ERR_INVALID_ARG, "effective_length not in the batch mask");
+  std::vector<int32_t> lt((size_t)b->n_bufs * 6);
+  if (!lt.empty()) HIP_TRY(hipMemcpy(lt.data(), b->d_efflen, lt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int32_t i = 0; i < b->n_bufs; ++i)
+    for (int j = 0; j < 3; ++j) {
+      // TAudioMath::SamplesToMs is float arithmetic (AudioMath.inl:134-137); seconds = ms / 1000.0
+      // silent leading samples = index of the first sample above the floor (all of them when there is none);
+      // the trailing scan stops above that sample (SampleAnalyser.cpp:1731-1746)
+      const int64_t first = lt[(size_t)i * 6 + 2 * j], last = lt[(size_t)i * 6 + 2 * j + 1];
+      const int64_t lead = (last < 0) ? b->used[i] : first, trail = (last < 0) ? 0 : b->used[i] - 1 - last;
+      const int samples = (int)(b->used[i] - lead - trail);
+      const float ms = (float)samples / ((float)b->plan->desc.sample_rate / 1000.0f);
+      seconds[(size_t)i * 3 + j] = (b->buf_status[i] == AFX_OK && b->used[i] > 0) ? (double)ms / 1000.0 : 0.0;
+    }
+  return AFX_OK;
+}
+
+}  // namespace host
+}  // namespace afx
+
 extern "C" {
 
 int afx_batch_fetch_samples(afx_batch* b, int32_t buf, double* dst, int64_t n) {
@@ -64,20 +88,8 @@ int afx_batch_fetch(afx_batch* b, afx_out* out) {
   if (out->frame_offset) std::memcpy(out->frame_offset, b->frame_offset.data(), b->frame_offset.size() * sizeof(int64_t));
   if (out->buf_status) std::memcpy(out->buf_status, b->buf_status.data(), b->buf_status.size() * sizeof(int32_t));
   if (out->effective_length) {
-    if (!b->d_efflen) return fail(AFX_ERR_INVALID_ARG, "effective_length not in the batch mask");
-    std::vector<int32_t> lt((size_t)b->n_bufs * 6);
-    if (!lt.empty()) HIP_TRY(hipMemcpy(lt.data(), b->d_efflen, lt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int32_t i = 0; i < b->n_bufs; ++i)
-      for (int j = 0; j < 3; ++j) {
-        // TAudioMath::SamplesToMs is float arithmetic (AudioMath.inl:134-137); seconds = ms / 1000.0
-        // silent leading samples = index of the first sample above the floor (all of them when there is none);
-        // the trailing scan stops above that sample (SampleAnalyser.cpp:1731-1746)
-        const int64_t first = lt[(size_t)i * 6 + 2 * j], last = lt[(size_t)i * 6 + 2 * j + 1];
-        const int64_t lead = (last < 0) ? b->used[i] : first, trail = (last < 0) ? 0 : b->used[i] - 1 - last;
-        const int samples = (int)(b->used[i] - lead - trail);
-        const float ms = (float)samples / ((float)b->plan->desc.sample_rate / 1000.0f);
-        out->effective_length[(size_t)i * 3 + j] = (b->buf_status[i] == AFX_OK && b->used[i] > 0) ? (double)ms / 1000.0 : 0.0;
-      }
+    const int st = effective_length_seconds(b, out->effective_length);
+    if (st != AFX_OK) return st;
   }
   const int64_t F = b->total_frames;
   if (F == 0) return AFX_OK;

@@ -11,24 +11,6 @@
 
 using namespace afx::host;
 
-namespace {
-
-// at least `bytes` of page-locked host memory in w->h_high: the block's transfer is a direct DMA, and no pageable
-// buffer of this call is still being read or written when it returns early
-hipError_t reserve_staging(Workspace* w, size_t bytes) {
-  if (bytes <= w->h_high_cap) return hipSuccess;
-  if (w->h_high) hipHostFree(w->h_high);
-  w->h_high = nullptr;
-  w->h_high_cap = 0;
-  const size_t want = bytes + bytes / 4 + 4096;
-  const hipError_t e = hipHostMalloc(&w->h_high, want, hipHostMallocDefault);
-  if (e != hipSuccess) { w->h_high = nullptr; return e; }
-  w->h_high_cap = want;
-  return hipSuccess;
-}
-
-}  // namespace
-
 extern "C" {
 
 int afx_batch_fetch_high_level(afx_batch* b, const afx_load_info* levels, afx_high_out* out) {
@@ -45,7 +27,7 @@ int afx_batch_fetch_high_level(afx_batch* b, const afx_load_info* levels, afx_hi
   const size_t doubles = n_scalars + n_signature + 2 * frames;
   const size_t block_bytes = doubles * sizeof(double), level_bytes = n * 2 * sizeof(float);
   HIP_TRY(ws_reserve(b->plan, b->ws->high, block_bytes + level_bytes));
-  HIP_TRY(reserve_staging(b->ws, block_bytes + level_bytes));
+  HIP_TRY(ws_result_pin_reserve(b->ws, block_bytes + level_bytes));
   double* const d_block = (double*)b->ws->high.p;
   float* const d_levels = (float*)(d_block + doubles);
 

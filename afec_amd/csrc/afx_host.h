@@ -13,6 +13,8 @@
 //   afx_batch_fetch.cpp results back to the host, batch information, afx_batch_destroy
 //   afx_high_level.cpp  afx_batch_fetch_high_level (SampleAnalyser.cpp:1234-1606); its launcher is declared in
 //                       highlevel/afx_highlevel.h, and none of the files above refers to either
+//   afx_classification.cpp  afx_batch_fetch_classification_features (SampleClassificationDescriptors.cpp:395-561), the
+//                       features' names and silence values; its launcher is declared in classify/afx_classify.h
 //
 // Nothing here computes a descriptor: every kernel lives in the .hip files (afx_internal.h declares their launchers).
 #pragma once
@@ -136,8 +138,8 @@ struct Workspace {
   Buf rt_odf, rt_onsets, rt_scratch, rt_scalars, rt_stats, rt_polar;   // rhythm tracker (its host-filled tables lie in `tables`)
   Buf stat_tmp;                                                                 // half-wave statistics class
   Buf rs_files, rs_groups, rs_ngroups;                                          // sample-rate conversion (afx_resample.hip)
-  Buf high;                                                                     // afx_batch_fetch_high_level's result block (afx_high_level.cpp)
-  void* h_high = nullptr;         // ... and the page-locked host block it lands in (with the peak / rms pairs on their way up)
+  Buf high;                       // the result block of afx_batch_fetch_high_level / afx_batch_fetch_classification_features (one at a time: both are synchronous)
+  void* h_high = nullptr;         // ... and the page-locked host block it lands in (with the call's small inputs on their way up)
   size_t h_high_cap = 0;
   std::vector<Buf*> all_bufs();   // every Buf member above, each exactly once: ws_free and bytes() walk this list
   size_t bytes();
@@ -255,6 +257,7 @@ void ws_free(Workspace* w);
 // allocation is tried once more (they hold their capacity: a batch that failed for memory would otherwise fail again)
 hipError_t ws_reserve(afx_plan* plan, Workspace::Buf& b, size_t bytes);
 hipError_t ws_pin_reserve(Workspace* w, size_t bytes);   // at least `bytes` of page-locked host memory in w->h_pin
+hipError_t ws_result_pin_reserve(Workspace* w, size_t bytes);   // ... in w->h_high
 size_t pool_trim(afx_plan* plan);   // frees every idle pooled workspace of the plan; returns the bytes given back
 hipError_t wait_for_event(Workspace* ws, hipEvent_t ev);
 hipError_t wait_for_stream(Workspace* ws, hipStream_t stream);
@@ -303,6 +306,11 @@ struct BatchSource {
   bool wait_for_uploads = true;
 };
 int build_batch(afx_plan* plan, const BatchSource& src, afx_batch** out_batch);
+
+// ---- afx_batch_fetch.cpp ----
+// effectve_length_{48,24,12}dB of every buffer in seconds, [n_bufs][3], from the sample indices the run left in d_efflen
+// (the batch's stream must be idle).  What afx_batch_fetch hands out and afx_batch_fetch_classification_features uploads.
+int effective_length_seconds(afx_batch* b, double* seconds);
 
 // ---- afx_batch_run.cpp ----
 #if defined(AFX_STAMPS) && AFX_STAMPS

@@ -94,6 +94,20 @@ hipError_t ws_pin_reserve(Workspace* w, size_t bytes) {
   return hipSuccess;
 }
 
+// the block's transfer is a direct DMA, and no pageable buffer of the call is still being read or written when it
+// returns early
+hipError_t ws_result_pin_reserve(Workspace* w, size_t bytes) {
+  if (bytes <= w->h_high_cap) return hipSuccess;
+  if (w->h_high) hipHostFree(w->h_high);
+  w->h_high = nullptr;
+  w->h_high_cap = 0;
+  const size_t want = bytes + bytes / 4 + 4096;
+  const hipError_t e = hipHostMalloc(&w->h_high, want, hipHostMallocDefault);
+  if (e != hipSuccess) { w->h_high = nullptr; return e; }
+  w->h_high_cap = want;
+  return hipSuccess;
+}
+
 size_t pool_trim(afx_plan* plan) {
   std::vector<Workspace*> idle;
   {

@@ -430,6 +430,47 @@ typedef struct {
  * AFX_ERR_INVALID_ARG when the batch's mask lacks one of AFX_D_HIGH_LEVEL_INPUTS.  Synchronous. */
 int afx_batch_fetch_high_level(afx_batch* batch, const afx_load_info* levels /* [n_bufs] or NULL */, afx_high_out* out);
 
+/* ---- classification features: TSampleClassificationDescriptors, SampleClassificationDescriptors.cpp:395-561 ---- *
+ * The vector every model of the reference is trained, tested and evaluated on (ModelCreator.cpp:234-251,
+ * SampleAnalyser.cpp:1076), gathered on the GPU from what a batch holds in device memory after afx_batch_run (one kernel,
+ * one transfer of 13 440 bytes per file); no mask bit of its own, nothing added to what afx_batch_run launches.  The models,
+ * their normalisation and outlier clipping (state of the model file) are not part of it.  T = 48 time positions: frames
+ * 0..43, 64, 128, 256, 512 (sTimeSeries); 14 merged bands (sSpectrumBands, as the high-level signature).  In this order:
+ *    672  spectrum_signature_b<b>_t<frame>   frame sTimeSeries[i] of frequency_bands, the bands of merged band b summed
+ *                                            and divided by their count, pow(1.25 v, 1/6); band outer, time inner
+ *    288  <series>_t<i>                      frames sTimeSeries[i] of spectral_rms, spectral_flatness, spectral_flux,
+ *                                            spectral_contrast, spectral_complexity, f0_confidence
+ *     42  <series>_<stat>                    min, max, mean, variance, flatness, dmean, dvariance of the same six
+ *    588  <series>_<stat>_b<band>            the same seven per band (band outer) of spectral_rms_bands,
+ *                                            spectral_flatness_bands, spectral_flux_bands, spectral_complexity_bands,
+ *                                            spectral_contrast_bands, cepstrum_bands
+ *     55  amplitude_rms_t<i>, amplitude_rms_<stat>;   7  amplitude_silence_<stat>
+ *      7  rhythm_{complex,percussive}_tempo_confidence, .._onset_contrast, .._onset_strength, effectve_length_12dB
+ *     21  padding_<k>                        the spectral_rms mean, up to 35 x 48 values
+ * The signature's names carry the frame NUMBER (_t64), every other time series the INDEX (_t44): the reference's names.
+ * A time position the file has no frame for holds the value of one frame of 2 048 zeros (what the reference's half second
+ * of silence becomes in LoadSample, :326-360): afx_plan_get_silence_features; the signature's band b takes
+ * frequency_bands[b] of that frame (band b of the 28, not the merged band, :466).
+ * The reference throws on a NaN or an infinity in any feature and the file fails; here the fetch reports per buffer how
+ * many of its values are not finite and the caller decides.  A buffer without frames (empty, or refused: buf_status)
+ * gets zeros and count 0. */
+#define AFX_CF_TIME_FRAMES 48
+#define AFX_NUM_CLASSIFICATION_FEATURES 1680
+#define AFX_NUM_CF_SILENCE 21 /* frequency_bands[0..13], then spectral_rms, _flatness, _flux, _contrast, _complexity, f0_confidence, amplitude_rms */
+/* the bits a batch's mask must hold for the fetch (all of them) */
+#define AFX_D_CLASSIFICATION_INPUTS                                                                                      \
+  (AFX_D_MFCC | AFX_D_SPECTRAL_RMS | AFX_D_SPECTRAL_FLATNESS | AFX_D_SPECTRAL_FLUX | AFX_D_SPECTRUM_BANDS |              \
+   AFX_D_BAND_FEATURES | AFX_D_AMPLITUDE_RMS | AFX_D_AMPLITUDE_SILENCE | AFX_D_SPECTRAL_COMPLEXITY | AFX_D_F0 |          \
+   AFX_D_STATISTICS | AFX_D_EFFECTIVE_LENGTH | AFX_D_RHYTHM)
+/* After afx_batch_run (before the first run: AFX_ERR_INVALID_ARG), any number of times; AFX_ERR_INVALID_ARG when the
+ * batch's mask lacks one of AFX_D_CLASSIFICATION_INPUTS.  Synchronous. */
+int afx_batch_fetch_classification_features(afx_batch* batch, double* features /* [n_bufs][AFX_NUM_CLASSIFICATION_FEATURES] */,
+                                            int32_t* non_finite /* [n_bufs] or NULL */, int32_t* status /* [n_bufs] or NULL: repeats buf_status */);
+/* the name of feature `index` as the reference's kExtractFeatureNames pass gives it, NUL-terminated; returns its length
+ * without the NUL, or AFX_ERR_INVALID_ARG (index out of range, capacity too small).  Touches no device. */
+int afx_classification_feature_name(int32_t index, char* dst, int32_t capacity);
+int afx_plan_get_silence_features(const afx_plan* plan, double* out /* [AFX_NUM_CF_SILENCE] */);
+
 /* Page-locked host memory for PCM and result arrays: transfers from / to such buffers run at the
  * host link's rate (pageable memory is staged by the runtime at a fraction of it). */
 void* afx_host_alloc(int64_t bytes);
