@@ -83,6 +83,8 @@ EXPORTS = [
     "afx_plan_set_blocking_wait", "afx_batch_get_info", "afx_plan_probe_device", "afx_device_count",
     "afx_batch_fetch_high_level",
     "afx_batch_fetch_classification_features", "afx_classification_feature_name", "afx_plan_get_silence_features",
+    "afx_model_create_from_lightgbm", "afx_model_destroy", "afx_model_get_info", "afx_batch_fetch_class_signature",
+    "afx_model_evaluate_features",
 ]
 RAW_I16, RAW_I24, RAW_F32, RAW_I32, RAW_F64 = 0, 1, 2, 3, 4
 
@@ -246,6 +248,13 @@ def load_library():
     L.afx_batch_fetch_classification_features.argtypes = [vp, vp, vp, vp]
     L.afx_classification_feature_name.argtypes = [i32, ctypes.c_char_p, i32]
     L.afx_plan_get_silence_features.argtypes = [vp, vp]
+    L.afx_model_create_from_lightgbm.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t), i32, vp, vp, vp,
+                                                 i32, ctypes.c_double, ctypes.POINTER(vp)]
+    L.afx_model_destroy.argtypes = [vp]
+    L.afx_model_destroy.restype = None
+    L.afx_model_get_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
+    L.afx_batch_fetch_class_signature.argtypes = [vp, vp, vp, vp, vp]
+    L.afx_model_evaluate_features.argtypes = [vp, vp, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -426,6 +435,56 @@ class Plan:
         return b, infos
 
 
+class Model:
+    """afx_model: a bagging of LightGBM models on the plan's device, with the normalisation and the outlier limits of the
+    reference's model file (afx_model_create_from_lightgbm).  texts: the models' LightGBM v3 texts (str or bytes); scale,
+    offset, limits: [1680] each; the early stop's defaults are LightGBM's, which the reference evaluates with."""
+
+    def __init__(self, plan, texts, scale, offset, limits, early_stop_freq=10, early_stop_margin=10.0):
+        self.L = plan.L
+        raw = [t.encode() if isinstance(t, str) else bytes(t) for t in texts]
+        n = len(raw)
+        ptrs = (ctypes.c_char_p * max(1, n))(*raw)
+        lens = (ctypes.c_size_t * max(1, n))(*[len(t) for t in raw])
+        vectors = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (scale, offset, limits)]
+        if any(v.size != NUM_CLASSIFICATION_FEATURES for v in vectors):
+            raise ValueError("scale, offset and limits hold NUM_CLASSIFICATION_FEATURES values each")
+        h = ctypes.c_void_p()
+        _check(self.L, self.L.afx_model_create_from_lightgbm(plan.h, ptrs, lens, n, vectors[0].ctypes.data, vectors[1].ctypes.data,
+                                                             vectors[2].ctypes.data, int(early_stop_freq), float(early_stop_margin),
+                                                             ctypes.byref(h)))
+        self.h = h
+        k, m = ctypes.c_int32(), ctypes.c_int32()
+        _check(self.L, self.L.afx_model_get_info(h, ctypes.byref(k), ctypes.byref(m), None))
+        self.n_classes, self.n_models = k.value, m.value
+        trees = np.zeros(self.n_models, dtype=np.int32)
+        _check(self.L, self.L.afx_model_get_info(h, None, None, trees.ctypes.data))
+        self.trees_per_model = trees.tolist()
+
+    def evaluate_features(self, features):
+        """afx_model_evaluate_features: the models on feature vectors of the caller's, [n][1680] ->
+        (signature float32 [n][n_classes], iterations_used [n][n_models], non_finite [n])"""
+        features = np.ascontiguousarray(features, dtype=np.float64).reshape(-1, NUM_CLASSIFICATION_FEATURES)
+        n = features.shape[0]
+        signature = np.zeros((max(1, n), self.n_classes), dtype=np.float32)
+        used = np.zeros((max(1, n), self.n_models), dtype=np.int32)
+        non_finite = np.zeros(max(1, n), dtype=np.int32)
+        _check(self.L, self.L.afx_model_evaluate_features(self.h, features.ctypes.data, n, signature.ctypes.data, used.ctypes.data,
+                                                          non_finite.ctypes.data))
+        return signature[:n], used[:n], non_finite[:n]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.afx_model_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Batch:
     """afx_batch: PCM resident in HBM, re-runnable."""
 
@@ -545,6 +604,17 @@ class Batch:
         _check(self.L, self.L.afx_batch_fetch_classification_features(self.h, features.ctypes.data, non_finite.ctypes.data,
                                                                       status.ctypes.data))
         return features[:n], non_finite[:n], status[:n]
+
+    def fetch_class_signature(self, model):
+        """afx_batch_fetch_class_signature: the reference's class signature of every buffer (SampleAnalyser.cpp:1075-1231)
+        -> (signature float32 [n_bufs][n_classes], iterations_used [n_bufs][n_models], non_finite [n_bufs])"""
+        n = self.n_bufs
+        signature = np.zeros((max(1, n), model.n_classes), dtype=np.float32)
+        used = np.zeros((max(1, n), model.n_models), dtype=np.int32)
+        non_finite = np.zeros(max(1, n), dtype=np.int32)
+        _check(self.L, self.L.afx_batch_fetch_class_signature(self.h, model.h, signature.ctypes.data, used.ctypes.data,
+                                                              non_finite.ctypes.data))
+        return signature[:n], used[:n], non_finite[:n]
 
     def close(self):
         if getattr(self, "h", None):

@@ -4,12 +4,17 @@
 // device memory, one device-to-host transfer of its result block.  As everywhere on the host side (afx_host.h), nothing
 // here computes a feature: the effective lengths go up as afx_batch_fetch hands them out, the block comes back.
 // Beside it what a caller needs to read the block: the features' names and the values a missing frame is filled with.
+// afx_batch_fetch_class_signature shares the launch (launch_features): the same kernel into the same block, the models'
+// kernel (gbdt/afx_gbdt.hip) behind it on the same stream, and only that kernel's few bytes per file come back
+// (SampleAnalyser.cpp:1075-1231).
 
 #include <cstdio>
 #include <cstring>
 
 #include "afx_host.h"
+#include "afx_model.h"
 #include "classify/afx_classify.h"
+#include "gbdt/afx_gbdt.h"
 
 using namespace afx::host;
 
@@ -51,6 +56,72 @@ int feature_name(int j, char* dst, size_t cap) {
   return std::snprintf(dst, cap, "padding_%d", j - kClassifyPaddingAt);
 }
 
+// The feature block of one fetch in the workspace's result buffers (device and page-locked host, same layout): the features
+// and the counts (what classification_features_kernel writes), behind them the effective lengths and the buffers' status
+// (what goes up), behind them `tail_bytes` for what the caller's own kernel writes.
+struct FeatureBlock {
+  size_t n = 0, n_features = 0;
+  size_t out_bytes = 0;     // features + counts
+  size_t tail_at = 0;       // where the caller's part starts (a multiple of 8)
+  char* d_block = nullptr;
+  char* block = nullptr;
+  afx::ClassifyArgs args{};
+};
+
+// Checks the batch, uploads the kernel's small inputs and launches it into the block, all on the batch's stream; nothing
+// is downloaded and nothing waited for behind the launch.  fb->n == 0: an empty batch, nothing launched.
+int launch_features(afx_batch* b, const char* who, size_t tail_bytes, FeatureBlock* fb) {
+  // a batch keeps AFX_D_STATISTICS apart from its mask: the statistics' device block stands for the bit
+  constexpr uint32_t kSeriesBits = AFX_D_CLASSIFICATION_INPUTS & ~(uint32_t)AFX_D_STATISTICS;
+  if ((b->mask & kSeriesBits) != kSeriesBits || (b->n_bufs > 0 && !b->d_stats))
+    return fail(AFX_ERR_INVALID_ARG, "the batch mask lacks an input of the classification features (AFX_D_CLASSIFICATION_INPUTS)");
+  if (!b->ran) return fail(AFX_ERR_INVALID_ARG, std::string(who) + " before afx_batch_run");
+  const size_t n = (size_t)b->n_bufs;
+  if (n == 0) return AFX_OK;
+  HIP_TRY(hipSetDevice(b->plan->desc.device));
+
+  const size_t n_features = n * afx::kClassifyFeatures, n_counts = (n + 1) & ~(size_t)1;
+  const size_t out_bytes = n_features * sizeof(double) + n_counts * sizeof(int32_t);
+  const size_t in_bytes = n * sizeof(double) + n * sizeof(int32_t);
+  const size_t tail_at = (out_bytes + in_bytes + 7) & ~(size_t)7;
+  HIP_TRY(ws_reserve(b->plan, b->ws->high, tail_at + tail_bytes));
+  HIP_TRY(ws_result_pin_reserve(b->ws, tail_at + tail_bytes));
+  char* const d_block = (char*)b->ws->high.p;
+  char* const block = (char*)b->ws->h_high;
+
+  HIP_TRY(hipStreamSynchronize(b->stream));   // the run's effective-length kernel has written d_efflen
+  {
+    std::vector<double> seconds(n * 3);
+    const int st = effective_length_seconds(b, seconds.data());
+    if (st != AFX_OK) return st;
+    double* const up = (double*)(block + out_bytes);
+    for (size_t i = 0; i < n; ++i) up[i] = seconds[i * 3 + 2];
+    std::memcpy(up + n, b->buf_status.data(), n * sizeof(int32_t));
+  }
+  afx::ClassifyArgs& a = fb->args;
+  a = afx::ClassifyArgs{};
+  a.rec = b->d_rec;
+  a.lay = b->lay;
+  a.frame_offset = b->d_frame_offset;
+  a.stats = b->d_stats;
+  a.rt_scalars = b->d_rt_scalars;
+  a.efflen12 = (const double*)(d_block + out_bytes);
+  a.status = (const int32_t*)(a.efflen12 + n);
+  a.n_bufs = b->n_bufs;
+  a.features = (double*)d_block;
+  a.non_finite = (int32_t*)(a.features + n_features);
+
+  HIP_TRY(hipMemcpyAsync(d_block + out_bytes, block + out_bytes, in_bytes, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(afx::launch_classification_features(a, b->stream));
+  fb->n = n;
+  fb->n_features = n_features;
+  fb->out_bytes = out_bytes;
+  fb->tail_at = tail_at;
+  fb->d_block = d_block;
+  fb->block = block;
+  return AFX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -72,55 +143,93 @@ int afx_plan_get_silence_features(const afx_plan* plan, double* out) {
 
 int afx_batch_fetch_classification_features(afx_batch* b, double* features, int32_t* non_finite, int32_t* status) {
   if (!b || !features) return fail(AFX_ERR_INVALID_ARG, "null argument");
-  // a batch keeps AFX_D_STATISTICS apart from its mask: the statistics' device block stands for the bit
-  constexpr uint32_t kSeriesBits = AFX_D_CLASSIFICATION_INPUTS & ~(uint32_t)AFX_D_STATISTICS;
-  if ((b->mask & kSeriesBits) != kSeriesBits || (b->n_bufs > 0 && !b->d_stats))
-    return fail(AFX_ERR_INVALID_ARG, "the batch mask lacks an input of the classification features (AFX_D_CLASSIFICATION_INPUTS)");
-  if (!b->ran) return fail(AFX_ERR_INVALID_ARG, "afx_batch_fetch_classification_features before afx_batch_run");
-  const size_t n = (size_t)b->n_bufs;
-  if (n == 0) return AFX_OK;
-  HIP_TRY(hipSetDevice(b->plan->desc.device));
-
-  // the block: the features and the counts (what comes back), behind them the effective lengths and the buffers' status
-  // (what goes up)
-  const size_t n_features = n * afx::kClassifyFeatures, n_counts = (n + 1) & ~(size_t)1;
-  const size_t out_bytes = n_features * sizeof(double) + n_counts * sizeof(int32_t);
-  const size_t in_bytes = n * sizeof(double) + n * sizeof(int32_t);
-  HIP_TRY(ws_reserve(b->plan, b->ws->high, out_bytes + in_bytes));
-  HIP_TRY(ws_result_pin_reserve(b->ws, out_bytes + in_bytes));
-  char* const d_block = (char*)b->ws->high.p;
-  char* const block = (char*)b->ws->h_high;
-
-  HIP_TRY(hipStreamSynchronize(b->stream));   // the run's effective-length kernel has written d_efflen
+  FeatureBlock fb;
+  const int st = launch_features(b, "afx_batch_fetch_classification_features", 0, &fb);
+  if (st != AFX_OK || fb.n == 0) return st;
   {
-    std::vector<double> seconds(n * 3);
-    const int st = effective_length_seconds(b, seconds.data());
-    if (st != AFX_OK) return st;
-    double* const up = (double*)(block + out_bytes);
-    for (size_t i = 0; i < n; ++i) up[i] = seconds[i * 3 + 2];
-    std::memcpy(up + n, b->buf_status.data(), n * sizeof(int32_t));
-  }
-  afx::ClassifyArgs a{};
-  a.rec = b->d_rec;
-  a.lay = b->lay;
-  a.frame_offset = b->d_frame_offset;
-  a.stats = b->d_stats;
-  a.rt_scalars = b->d_rt_scalars;
-  a.efflen12 = (const double*)(d_block + out_bytes);
-  a.status = (const int32_t*)(a.efflen12 + n);
-  a.n_bufs = b->n_bufs;
-  a.features = (double*)d_block;
-  a.non_finite = (int32_t*)(a.features + n_features);
-
-  HIP_TRY(hipMemcpyAsync(d_block + out_bytes, block + out_bytes, in_bytes, hipMemcpyHostToDevice, b->stream));
-  HIP_TRY(afx::launch_classification_features(a, b->stream));
-  {
-    const Download item{block, d_block, out_bytes};
+    const Download item{fb.block, fb.d_block, fb.out_bytes};
     HIP_TRY(download_through_plan(b, &item, 1));   // waits for the batch's stream first, then for the transfer
   }
-  std::memcpy(features, block, n_features * sizeof(double));
-  if (non_finite) std::memcpy(non_finite, block + n_features * sizeof(double), n * sizeof(int32_t));
-  if (status) std::memcpy(status, b->buf_status.data(), n * sizeof(int32_t));
+  std::memcpy(features, fb.block, fb.n_features * sizeof(double));
+  if (non_finite) std::memcpy(non_finite, fb.block + fb.n_features * sizeof(double), fb.n * sizeof(int32_t));
+  if (status) std::memcpy(status, b->buf_status.data(), fb.n * sizeof(int32_t));
+  return AFX_OK;
+}
+
+int afx_batch_fetch_class_signature(afx_batch* b, const afx_model* model, float* signature, int32_t* iterations_used, int32_t* nonfinite) {
+  if (!b || !model || !signature) return fail(AFX_ERR_INVALID_ARG, "null argument");
+  if (model->plan->desc.device != b->plan->desc.device) return fail(AFX_ERR_INVALID_ARG, "the model lives on another device than the batch");
+  // behind the feature block: the signatures, the iterations used, the counts (what comes back)
+  const size_t n = (size_t)b->n_bufs, n_classes = (size_t)model->dev.n_classes, n_models = (size_t)model->dev.n_models;
+  const size_t sig_bytes = (n * n_classes * sizeof(float) + 7) & ~(size_t)7;
+  const size_t tail_bytes = sig_bytes + (n * n_models + n) * sizeof(int32_t);
+  FeatureBlock fb;
+  const int st = launch_features(b, "afx_batch_fetch_class_signature", tail_bytes, &fb);
+  if (st != AFX_OK || fb.n == 0) return st;
+  afx::GbdtArgs g{};
+  g.model = model->dev;
+  g.features = fb.args.features;
+  g.frame_offset = b->d_frame_offset;
+  g.status = fb.args.status;
+  g.n_bufs = b->n_bufs;
+  g.signature = (float*)(fb.d_block + fb.tail_at);
+  g.iterations_used = (int32_t*)(fb.d_block + fb.tail_at + sig_bytes);
+  g.non_finite = g.iterations_used + n * n_models;
+  HIP_TRY(afx::launch_class_signature(g, b->stream));
+  char* const tail = fb.block + fb.tail_at;
+  {
+    const Download item{tail, fb.d_block + fb.tail_at, tail_bytes};
+    HIP_TRY(download_through_plan(b, &item, 1));
+  }
+  std::memcpy(signature, tail, n * n_classes * sizeof(float));
+  if (iterations_used) std::memcpy(iterations_used, tail + sig_bytes, n * n_models * sizeof(int32_t));
+  if (nonfinite) std::memcpy(nonfinite, tail + sig_bytes + n * n_models * sizeof(int32_t), n * sizeof(int32_t));
+  return AFX_OK;
+}
+
+int afx_model_evaluate_features(const afx_model* model, const double* features, int32_t n_vectors, float* signature,
+                                int32_t* iterations_used, int32_t* nonfinite) {
+  if (!model || n_vectors < 0 || (n_vectors > 0 && (!features || !signature))) return fail(AFX_ERR_INVALID_ARG, "bad argument");
+  if (n_vectors == 0) return AFX_OK;
+  HIP_TRY(hipSetDevice(model->plan->desc.device));
+  // one block of its own (this is not the crawl's path: no batch, no workspace): the vectors, a frame table that gives
+  // every vector one frame, a status of zeros; behind them what the kernel writes
+  const size_t n = (size_t)n_vectors, n_classes = (size_t)model->dev.n_classes, n_models = (size_t)model->dev.n_models;
+  const size_t feature_bytes = n * afx::kGbdtFeatures * sizeof(double), offset_bytes = (n + 1) * sizeof(int64_t);
+  const size_t status_bytes = (n * sizeof(int32_t) + 7) & ~(size_t)7;
+  const size_t sig_bytes = (n * n_classes * sizeof(float) + 7) & ~(size_t)7;
+  const size_t in_bytes = feature_bytes + offset_bytes + status_bytes;
+  const size_t out_bytes = sig_bytes + (n * n_models + n) * sizeof(int32_t);
+  std::vector<char> host(offset_bytes + status_bytes + out_bytes, 0);
+  for (size_t i = 0; i <= n; ++i) ((int64_t*)host.data())[i] = (int64_t)i;
+  char* d_block = nullptr;
+  {
+    const hipError_t e = hipMalloc((void**)&d_block, in_bytes + out_bytes);
+    if (e == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      return fail(AFX_ERR_OUT_OF_MEMORY, "device memory for the feature vectors");
+    }
+    HIP_TRY(e);
+  }
+  afx::GbdtArgs g{};
+  g.model = model->dev;
+  g.features = (const double*)d_block;
+  g.frame_offset = (const int64_t*)(d_block + feature_bytes);
+  g.status = (const int32_t*)(d_block + feature_bytes + offset_bytes);
+  g.n_bufs = n_vectors;
+  g.signature = (float*)(d_block + in_bytes);
+  g.iterations_used = (int32_t*)(d_block + in_bytes + sig_bytes);
+  g.non_finite = g.iterations_used + n * n_models;
+  hipError_t e = hipMemcpy(d_block, features, feature_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_block + feature_bytes, host.data(), offset_bytes + status_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = afx::launch_class_signature(g, nullptr);
+  char* const out = host.data() + offset_bytes + status_bytes;
+  if (e == hipSuccess) e = hipMemcpy(out, d_block + in_bytes, out_bytes, hipMemcpyDeviceToHost);   // waits for the kernel
+  (void)hipFree(d_block);
+  HIP_TRY(e);
+  std::memcpy(signature, out, n * n_classes * sizeof(float));
+  if (iterations_used) std::memcpy(iterations_used, out + sig_bytes, n * n_models * sizeof(int32_t));
+  if (nonfinite) std::memcpy(nonfinite, out + sig_bytes + n * n_models * sizeof(int32_t), n * sizeof(int32_t));
   return AFX_OK;
 }
 

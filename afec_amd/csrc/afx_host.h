@@ -14,7 +14,10 @@
 //   afx_high_level.cpp  afx_batch_fetch_high_level (SampleAnalyser.cpp:1234-1606); its launcher is declared in
 //                       highlevel/afx_highlevel.h, and none of the files above refers to either
 //   afx_classification.cpp  afx_batch_fetch_classification_features (SampleClassificationDescriptors.cpp:395-561), the
-//                       features' names and silence values; its launcher is declared in classify/afx_classify.h
+//                       features' names and silence values; its launcher is declared in classify/afx_classify.h.
+//                       afx_batch_fetch_class_signature beside it (the same launch, then gbdt/afx_gbdt.h's)
+//   afx_model.cpp       afx_model_create_from_lightgbm / _get_info / _destroy: LightGBM's text into the arrays of
+//                       gbdt/afx_gbdt.h (afx_model.h); no launch, so it links against the device mock as it is
 //
 // Nothing here computes a descriptor: every kernel lives in the .hip files (afx_internal.h declares their launchers).
 #pragma once

@@ -1,0 +1,345 @@
+// afec_amd/csrc/afx_model.cpp -- afx_model_create_from_lightgbm, afx_model_get_info, afx_model_destroy: the models of the
+// reference's class signature (a TBaggingClassificationModel of TGbdtClassificationModel, Models/Bagging.h, Models/GBDT.cpp)
+// read from LightGBM's text form into the flat arrays of gbdt/afx_gbdt.h and uploaded once, with the Normalizer's scale and
+// offset and the outlier limits (ClassificationTestDataItem.cpp:36-41).  Plain host code: nothing here evaluates a tree,
+// and nothing here launches (afx_batch_fetch_class_signature is in afx_classification.cpp beside the feature fetch whose
+// launch it shares).  The reader checks every index the kernel will follow, so a text that is not what it claims to be is
+// refused here and never walked on the device.
+
+#include <charconv>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+
+#include "afx_host.h"
+#include "afx_model.h"
+
+using namespace afx::host;
+
+namespace afx {
+namespace host {
+namespace {
+
+constexpr int32_t kMaxLeaves = 1 << 16;      // per tree: far above anything LightGBM's num_leaves is set to
+constexpr size_t kMaxTrees = 1 << 22;        // per bagging: keeps every int32 offset below 2^31 with room to spare
+constexpr size_t kMaxNodes = (size_t)1 << 28;
+
+struct Fail {
+  int status;
+  std::string why;
+};
+
+// the next line of s from `pos` (without its end; a \r before it is dropped); false at `end`
+bool next_line(const std::string& s, size_t end, size_t* pos, std::string* line) {
+  if (*pos >= end) return false;
+  size_t nl = s.find('\n', *pos);
+  if (nl == std::string::npos || nl > end) nl = end;
+  size_t stop = nl;
+  if (stop > *pos && s[stop - 1] == '\r') --stop;
+  line->assign(s, *pos, stop - *pos);
+  *pos = nl + 1;
+  return true;
+}
+
+bool blank(const std::string& line) { return line.find_first_not_of(" \t") == std::string::npos; }
+
+// Numbers are read with std::from_chars: no locale (a host application's LC_NUMERIC does not reach it), no leading
+// blanks or '+', and for doubles the correctly rounded value, as the fast_double_parser LightGBM reads these lists with.
+// A token may hold digits, a sign, a point and an exponent only: no hexadecimal floats, no "inf" or "nan" spellings.
+// (LightGBM writes a threshold with %.17g and a leaf value likewise; neither is ever infinite in a model it saved.)
+
+// the token of blanks-separated list `v` at *pos -> [first, last); false at the end of the list
+bool next_token(const std::string& v, size_t* pos, const char** first, const char** last) {
+  size_t a = v.find_first_not_of(" \t", *pos);
+  if (a == std::string::npos) return false;
+  size_t b = v.find_first_of(" \t", a);
+  if (b == std::string::npos) b = v.size();
+  *first = v.data() + a;
+  *last = v.data() + b;
+  *pos = b;
+  return true;
+}
+
+bool token_int(const char* first, const char* last, long lo, long hi, long* out) {
+  long x = 0;
+  const std::from_chars_result r = std::from_chars(first, last, x, 10);
+  if (r.ec != std::errc() || r.ptr != last || x < lo || x > hi) return false;
+  *out = x;
+  return true;
+}
+
+bool token_double(const char* first, const char* last, double* out) {
+  for (const char* p = first; p != last; ++p)
+    if (!((*p >= '0' && *p <= '9') || *p == '-' || *p == '+' || *p == '.' || *p == 'e' || *p == 'E')) return false;
+  double x = 0.0;
+  const std::from_chars_result r = std::from_chars(first, last, x, std::chars_format::general);
+  if (r.ec != std::errc() || r.ptr != last || !std::isfinite(x)) return false;
+  *out = x;
+  return true;
+}
+
+bool to_int(const std::string& v, long lo, long hi, long* out) {
+  size_t pos = 0;
+  const char *first, *last;
+  return next_token(v, &pos, &first, &last) && token_int(first, last, lo, hi, out) && !next_token(v, &pos, &first, &last);
+}
+
+// `n` numbers separated by blanks, no more and no fewer, appended to dst
+bool int_list(const std::string& v, size_t n, long lo, long hi, std::vector<int32_t>* dst) {
+  size_t pos = 0;
+  const char *first, *last;
+  for (size_t i = 0; i < n; ++i) {
+    long x = 0;
+    if (!next_token(v, &pos, &first, &last) || !token_int(first, last, lo, hi, &x)) return false;
+    dst->push_back((int32_t)x);
+  }
+  return !next_token(v, &pos, &first, &last);
+}
+
+bool double_list(const std::string& v, size_t n, std::vector<double>* dst) {
+  size_t pos = 0;
+  const char *first, *last;
+  for (size_t i = 0; i < n; ++i) {
+    double x = 0.0;
+    if (!next_token(v, &pos, &first, &last) || !token_double(first, last, &x)) return false;
+    dst->push_back(x);
+  }
+  return !next_token(v, &pos, &first, &last);
+}
+
+typedef std::map<std::string, std::string> KeyValues;
+
+bool key_value(const std::string& line, KeyValues* kv) {
+  const size_t eq = line.find('=');
+  if (eq == std::string::npos) return false;
+  (*kv)[line.substr(0, eq)] = line.substr(eq + 1);
+  return true;
+}
+
+Fail parse(const std::string& s, ParsedModels* out) {
+  const size_t end = s.find("end of trees");
+  if (end == std::string::npos) return {AFX_ERR_INVALID_ARG, "no 'end of trees' (a truncated text?)"};
+  size_t pos = 0;
+  std::string line;
+
+  // ---- the header, up to the first tree ----
+  KeyValues head;
+  bool saw_tree_line = false, have_line = false;
+  while ((have_line = next_line(s, end, &pos, &line))) {
+    if (line.compare(0, 5, "Tree=") == 0) break;
+    if (line == "tree") saw_tree_line = true;
+    else if (line == "average_output") head["average_output"] = "";
+    else if (!blank(line)) key_value(line, &head);
+  }
+  if (!saw_tree_line) return {AFX_ERR_INVALID_ARG, "not a LightGBM model text (no 'tree' line)"};
+  if (!head.count("version") || head["version"] != "v3") return {AFX_ERR_UNSUPPORTED, "not a version=v3 model"};
+  for (const char* key : {"num_class", "num_tree_per_iteration", "max_feature_idx", "objective"})
+    if (!head.count(key)) return {AFX_ERR_INVALID_ARG, std::string("no ") + key};
+  if (head.count("average_output")) return {AFX_ERR_UNSUPPORTED, "average_output (a random forest's mean) is not supported"};
+  long num_class = 0, per_iteration = 0, max_feature = 0;
+  if (!to_int(head["num_class"], 0, 1 << 20, &num_class) || !to_int(head["num_tree_per_iteration"], 0, 1 << 20, &per_iteration) ||
+      !to_int(head["max_feature_idx"], 0, 1 << 30, &max_feature))
+    return {AFX_ERR_INVALID_ARG, "num_class, num_tree_per_iteration or max_feature_idx is no number"};
+  if (max_feature != kGbdtFeatures - 1)
+    return {AFX_ERR_UNSUPPORTED, "max_feature_idx " + std::to_string(max_feature) + ": the models read 1 680 features"};
+  if (num_class < 2 || num_class > kGbdtMaxClasses || per_iteration != num_class)
+    return {AFX_ERR_UNSUPPORTED, "num_class " + std::to_string(num_class) + " with " + std::to_string(per_iteration) + " trees per iteration"};
+  if (out->n_models() > 0 && out->n_classes != (int32_t)num_class)
+    return {AFX_ERR_UNSUPPORTED, "the models disagree on num_class"};
+  int32_t objective = kGbdtSoftmax;
+  double sigmoid = 1.0;
+  {
+    const std::string& o = head["objective"];
+    const size_t sp = o.find(' ');
+    const std::string name = o.substr(0, sp);
+    if (name == "multiclass") objective = kGbdtSoftmax;
+    else if (name == "multiclassova" || name == "multiclass_ova") objective = kGbdtOneVsAll;
+    else return {AFX_ERR_UNSUPPORTED, "objective '" + name + "'"};
+    if (objective == kGbdtOneVsAll) {
+      // multiclass_objective.hpp:197-215: without a positive sigmoid LightGBM refuses the model
+      const size_t at = o.find(" sigmoid:");
+      std::vector<double> v;
+      if (at == std::string::npos || !double_list(o.substr(at + 9, o.find(' ', at + 9) - (at + 9)), 1, &v) || !(v[0] > 0.0))
+        return {AFX_ERR_INVALID_ARG, "multiclassova without a positive sigmoid"};
+      sigmoid = v[0];
+    }
+  }
+
+  // ---- the trees: "Tree=<t>", key=value lines, a blank line ----
+  ParsedModels add;   // this model's arrays, offsets from 0
+  size_t t = 0;
+  while (have_line) {
+    long index = -1;
+    if (line.compare(0, 5, "Tree=") != 0 || !to_int(line.substr(5), 0, (long)kMaxTrees, &index) || (size_t)index != t)
+      return {AFX_ERR_INVALID_ARG, "tree " + std::to_string(t) + ": 'Tree=" + std::to_string(t) + "' expected"};
+    const std::string tag = "tree " + std::to_string(t) + ": ";
+    KeyValues kv;
+    while ((have_line = next_line(s, end, &pos, &line)) && !blank(line))
+      if (!key_value(line, &kv)) return {AFX_ERR_INVALID_ARG, tag + "a line without '='"};
+    while (have_line && blank(line)) have_line = next_line(s, end, &pos, &line);
+
+    long n = 0, num_cat = 0, is_linear = 0;
+    if (!kv.count("num_leaves") || !to_int(kv["num_leaves"], 1, kMaxLeaves, &n)) return {AFX_ERR_INVALID_ARG, tag + "num_leaves"};
+    if (kv.count("num_cat") && !to_int(kv["num_cat"], 0, 1 << 30, &num_cat)) return {AFX_ERR_INVALID_ARG, tag + "num_cat"};
+    if (kv.count("is_linear") && !to_int(kv["is_linear"], 0, 1, &is_linear)) return {AFX_ERR_INVALID_ARG, tag + "is_linear"};
+    if (num_cat != 0) return {AFX_ERR_UNSUPPORTED, tag + "categorical splits"};
+    if (is_linear != 0) return {AFX_ERR_UNSUPPORTED, tag + "a linear tree"};
+    const size_t node0 = add.threshold.size(), leaf0 = add.leaf_value.size(), inner = (size_t)n - 1;
+    if (t >= kMaxTrees || node0 + inner > kMaxNodes) return {AFX_ERR_UNSUPPORTED, tag + "too many trees or nodes"};
+    add.num_leaves.push_back((int32_t)n);
+    add.node_first.push_back((int32_t)node0);
+    add.leaf_first.push_back((int32_t)leaf0);
+    if (!kv.count("leaf_value") || !double_list(kv["leaf_value"], (size_t)n, &add.leaf_value))
+      return {AFX_ERR_INVALID_ARG, tag + "leaf_value does not hold num_leaves finite numbers"};
+    if (n > 1) {
+      for (const char* key : {"split_feature", "threshold", "decision_type", "left_child", "right_child"})
+        if (!kv.count(key)) return {AFX_ERR_INVALID_ARG, tag + "no " + key};
+      if (!int_list(kv["split_feature"], inner, 0, max_feature, &add.split_feature))
+        return {AFX_ERR_INVALID_ARG, tag + "split_feature does not hold num_leaves - 1 feature indices"};
+      if (!double_list(kv["threshold"], inner, &add.threshold)) return {AFX_ERR_INVALID_ARG, tag + "threshold"};
+      if (!int_list(kv["decision_type"], inner, 0, 15, &add.decision_type)) return {AFX_ERR_INVALID_ARG, tag + "decision_type"};
+      if (!int_list(kv["left_child"], inner, -n, n - 2, &add.left_child)) return {AFX_ERR_INVALID_ARG, tag + "left_child"};
+      if (!int_list(kv["right_child"], inner, -n, n - 2, &add.right_child)) return {AFX_ERR_INVALID_ARG, tag + "right_child"};
+      for (size_t i = 0; i < inner; ++i) {
+        if (add.decision_type[node0 + i] & 1) return {AFX_ERR_UNSUPPORTED, tag + "a categorical split"};
+        // an inner child lies behind its parent (Tree::Split numbers them so): every walk ends.  A leaf ~c lies in [0, n)
+        // by the list's bounds.
+        for (const int32_t c : {add.left_child[node0 + i], add.right_child[node0 + i]})
+          if (c >= 0 && (size_t)c <= i) return {AFX_ERR_INVALID_ARG, tag + "a child that does not lie behind its parent"};
+      }
+    }
+    ++t;
+  }
+  if (t == 0 || t % (size_t)num_class) return {AFX_ERR_INVALID_ARG, std::to_string(t) + " trees for " + std::to_string(num_class) + " per iteration"};
+  if (out->num_leaves.size() + t > kMaxTrees || out->threshold.size() + add.threshold.size() > kMaxNodes)
+    return {AFX_ERR_UNSUPPORTED, "too many trees or nodes"};
+
+  // ---- behind the models before ----
+  const int32_t node_base = (int32_t)out->threshold.size(), leaf_base = (int32_t)out->leaf_value.size();
+  out->n_classes = (int32_t)num_class;
+  out->objective.push_back(objective);
+  out->sigmoid.push_back(sigmoid);
+  out->tree_first.push_back(out->tree_first.back() + (int32_t)t);
+  for (size_t i = 0; i < t; ++i) {
+    out->num_leaves.push_back(add.num_leaves[i]);
+    out->node_first.push_back(node_base + add.node_first[i]);
+    out->leaf_first.push_back(leaf_base + add.leaf_first[i]);
+  }
+  out->split_feature.insert(out->split_feature.end(), add.split_feature.begin(), add.split_feature.end());
+  out->decision_type.insert(out->decision_type.end(), add.decision_type.begin(), add.decision_type.end());
+  out->left_child.insert(out->left_child.end(), add.left_child.begin(), add.left_child.end());
+  out->right_child.insert(out->right_child.end(), add.right_child.begin(), add.right_child.end());
+  out->threshold.insert(out->threshold.end(), add.threshold.begin(), add.threshold.end());
+  out->leaf_value.insert(out->leaf_value.end(), add.leaf_value.begin(), add.leaf_value.end());
+  return {AFX_OK, ""};
+}
+
+template <typename T>
+size_t padded_bytes(const std::vector<T>& v) { return (v.size() * sizeof(T) + 15) & ~(size_t)15; }
+
+}  // namespace
+
+int parse_lightgbm_model(const char* text, size_t len, ParsedModels* out, std::string* why) {
+  if (!text || !out) {
+    if (why) *why = "null argument";
+    return AFX_ERR_INVALID_ARG;
+  }
+  const std::string s(text, strnlen(text, len));
+  const Fail f = parse(s, out);
+  if (why) *why = f.why;
+  return f.status;
+}
+
+}  // namespace host
+}  // namespace afx
+
+extern "C" {
+
+int afx_model_create_from_lightgbm(afx_plan* plan, const char* const* texts, const size_t* lens, int32_t n_models, const double* scale,
+                                   const double* offset, const double* limits, int32_t early_stop_freq, double early_stop_margin,
+                                   afx_model** out_model) {
+  if (!plan || !texts || !lens || !scale || !offset || !limits || !out_model) return fail(AFX_ERR_INVALID_ARG, "null argument");
+  *out_model = nullptr;
+  if (n_models < 1 || n_models > afx::kGbdtMaxModels) return fail(AFX_ERR_INVALID_ARG, "n_models out of range (1..64)");
+  if (early_stop_freq < 1 || std::isnan(early_stop_margin)) return fail(AFX_ERR_INVALID_ARG, "early_stop_freq < 1 or a NaN margin");
+  for (int j = 0; j < afx::kGbdtFeatures; ++j)
+    if (!std::isfinite(scale[j]) || !std::isfinite(offset[j]) || !(limits[j] > 0.0) || !std::isfinite(limits[j]))
+      return fail(AFX_ERR_INVALID_ARG, "scale / offset not finite or a limit not positive at feature " + std::to_string(j));
+  ParsedModels p;
+  for (int i = 0; i < n_models; ++i) {
+    std::string why;
+    const int st = parse_lightgbm_model(texts[i], lens[i], &p, &why);
+    if (st != AFX_OK) return fail(st, "model " + std::to_string(i) + ": " + why);
+  }
+
+  // one block: the doubles first, then the int32 arrays, each at a multiple of 16 bytes
+  const std::vector<double> v_scale(scale, scale + afx::kGbdtFeatures), v_offset(offset, offset + afx::kGbdtFeatures),
+      v_limits(limits, limits + afx::kGbdtFeatures);
+  struct Part { const void* src; size_t bytes, padded; const void** slot; };
+  afx::GbdtModel dev{};
+  dev.n_models = n_models;
+  dev.n_classes = p.n_classes;
+  dev.early_stop_freq = early_stop_freq;
+  dev.early_stop_margin = early_stop_margin;
+#define AFX_PART(vec, member) Part{(vec).data(), (vec).size() * sizeof((vec)[0]), padded_bytes(vec), (const void**)&dev.member}
+  const Part parts[] = {AFX_PART(v_scale, scale), AFX_PART(v_offset, offset), AFX_PART(v_limits, limits),
+                        AFX_PART(p.sigmoid, sigmoid), AFX_PART(p.threshold, threshold), AFX_PART(p.leaf_value, leaf_value),
+                        AFX_PART(p.tree_first, tree_first), AFX_PART(p.objective, objective), AFX_PART(p.num_leaves, num_leaves),
+                        AFX_PART(p.node_first, node_first), AFX_PART(p.leaf_first, leaf_first),
+                        AFX_PART(p.split_feature, split_feature), AFX_PART(p.decision_type, decision_type),
+                        AFX_PART(p.left_child, left_child), AFX_PART(p.right_child, right_child)};
+#undef AFX_PART
+  size_t total = 16;   // a model of one-leaf trees has no node: its empty arrays still point into the block
+  for (const Part& part : parts) total += part.padded;
+  std::vector<char> image(total, 0);
+  HIP_TRY(hipSetDevice(plan->desc.device));
+  void* d_block = nullptr;
+  {
+    const hipError_t e = hipMalloc(&d_block, total);
+    if (e == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      return fail(AFX_ERR_OUT_OF_MEMORY, "device memory for the model");
+    }
+    HIP_TRY(e);
+  }
+  size_t at = 0;
+  for (const Part& part : parts) {
+    if (part.bytes) std::memcpy(image.data() + at, part.src, part.bytes);
+    *part.slot = (char*)d_block + at;
+    at += part.padded;
+  }
+  {
+    const hipError_t e = hipMemcpy(d_block, image.data(), total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      hipFree(d_block);
+      return hip_fail(e, "hipMemcpy of the model");
+    }
+  }
+  afx_model* m = new afx_model();
+  m->plan = plan;
+  plan->refs.fetch_add(1);
+  m->d_block = d_block;
+  m->dev = dev;
+  for (int i = 0; i < n_models; ++i) m->trees.push_back(p.tree_first[i + 1] - p.tree_first[i]);
+  *out_model = m;
+  return AFX_OK;
+}
+
+int afx_model_get_info(const afx_model* model, int32_t* n_classes, int32_t* n_models, int32_t* trees_per_model) {
+  if (!model) return fail(AFX_ERR_INVALID_ARG, "null argument");
+  if (n_classes) *n_classes = model->dev.n_classes;
+  if (n_models) *n_models = model->dev.n_models;
+  if (trees_per_model) std::memcpy(trees_per_model, model->trees.data(), model->trees.size() * sizeof(int32_t));
+  return AFX_OK;
+}
+
+void afx_model_destroy(afx_model* model) {
+  if (!model) return;
+  hipSetDevice(model->plan->desc.device);
+  hipFree(model->d_block);
+  plan_release(model->plan);
+  delete model;
+}
+
+}  // extern "C"

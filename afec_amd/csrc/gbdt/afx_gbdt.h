@@ -1,0 +1,58 @@
+// afec_amd/csrc/gbdt/afx_gbdt.h -- the class signature's kernel (afx_gbdt.hip) and its launcher, shared with the entry
+// points of afx_model.cpp (which fills GbdtModel) and afx_classification.cpp (which launches).  Kept apart from
+// afx_internal.h for the reason highlevel/afx_highlevel.h gives: that header's launchers are the set a device mock has to
+// implement, and this one is not part of it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../afx_internal.h"
+
+namespace afx {
+
+constexpr int kGbdtFeatures = 1680;    // AFX_NUM_CLASSIFICATION_FEATURES: what every model's max_feature_idx + 1 must be
+constexpr int kGbdtMaxClasses = 64;    // a class is a lane where the raw scores are summed
+constexpr int kGbdtMaxModels = 64;     // ... and a model is one where iterations_used is written
+constexpr int kGbdtSoftmax = 0, kGbdtOneVsAll = 1;   // ConvertOutput of "multiclass" / "multiclassova"
+
+// One bagging of LightGBM models in device memory, flat: tree t of model m is tree_first[m] + t of the per-tree arrays
+// (t = iteration * n_classes + class), node i of a tree is node_first[tree] + i of the per-node arrays, leaf j is
+// leaf_first[tree] + j of leaf_value.  A child >= 0 is a node of the same tree, < 0 the leaf ~child (tree.h:690-702).
+// afx_model.cpp has checked every index: a split feature lies in [0, kGbdtFeatures), a node's inner children lie behind
+// it and inside the tree (every walk ends), a leaf inside the tree's leaves.
+struct GbdtModel {
+  int32_t n_models, n_classes;
+  int32_t early_stop_freq;        // round_period: the margin is tested after every this many iterations (>= 1)
+  double early_stop_margin;       // margin_threshold
+  const int32_t* tree_first;      // [n_models + 1]
+  const int32_t* objective;       // [n_models]: kGbdtSoftmax / kGbdtOneVsAll
+  const double* sigmoid;          // [n_models]
+  const int32_t* num_leaves;      // [trees]
+  const int32_t* node_first;      // [trees]
+  const int32_t* leaf_first;      // [trees]
+  const int32_t* split_feature;   // [nodes]
+  const int32_t* decision_type;   // [nodes]: bit 1 default left, bits 2..3 the missing type (none, zero, NaN)
+  const int32_t* left_child;      // [nodes]
+  const int32_t* right_child;     // [nodes]
+  const double* threshold;        // [nodes]
+  const double* leaf_value;       // [leaves]
+  const double* scale;            // [kGbdtFeatures]: the Normalizer's A
+  const double* offset;           // [kGbdtFeatures]: ... and b
+  const double* limits;           // [kGbdtFeatures]: the outlier limits, > 0
+};
+
+struct GbdtArgs {
+  GbdtModel model;
+  const double* features;         // [n_bufs][kGbdtFeatures]: what classification_features_kernel wrote
+  const int64_t* frame_offset;    // [n_bufs + 1], device
+  const int32_t* status;          // [n_bufs]: buf_status
+  int32_t n_bufs;
+  float* signature;               // [n_bufs][n_classes]
+  int32_t* iterations_used;       // [n_bufs][n_models]
+  int32_t* non_finite;            // [n_bufs]
+};
+// one wave per buffer, on `stream`
+hipError_t launch_class_signature(const GbdtArgs& a, hipStream_t stream);
+
+}  // namespace afx

@@ -13,6 +13,7 @@
 #ifndef AFX_H
 #define AFX_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -470,6 +471,48 @@ int afx_batch_fetch_classification_features(afx_batch* batch, double* features /
  * without the NUL, or AFX_ERR_INVALID_ARG (index out of range, capacity too small).  Touches no device. */
 int afx_classification_feature_name(int32_t index, char* dst, int32_t capacity);
 int afx_plan_get_silence_features(const afx_plan* plan, double* out /* [AFX_NUM_CF_SILENCE] */);
+
+/* ---- class signature: the reference's models on the classification features, SampleAnalyser.cpp:1075-1231 ---- *
+ * What the reference stores as a file's class signature ("OneShot" / "Loop"): the 1 680 features above, normalised
+ * (x * scale + offset, the product rounded first: shark::Normalizer) and clipped to [-limits, +limits]
+ * (ClassificationTestDataItem.cpp:36-41), through a bagging of LightGBM models; per model Boosting::Predict with the
+ * "multiclass" prediction early stop (Models/GBDT.cpp:326-373: after every early_stop_freq iterations the evaluation ends
+ * when the two largest raw scores lie more than early_stop_margin apart; the reference runs with LightGBM's defaults, 10
+ * and 10.0), the objective's ConvertOutput (softmax for "multiclass", a sigmoid per class for "multiclassova"), a cast to
+ * float; then the float mean over the models in model order (Models/Bagging.h:192-217).
+ *
+ * afx_model_create_from_lightgbm reads n_models (1..64) LightGBM v3 text models (texts[i], lens[i] bytes, no NUL needed;
+ * the gzip members of the reference's .model file, decompressed) and uploads them once to the plan's device with the three
+ * vectors of AFX_NUM_CLASSIFICATION_FEATURES doubles.  AFX_ERR_UNSUPPORTED: categorical splits, linear trees, another
+ * feature count than 1 680 (max_feature_idx != 1679), models that disagree on num_class, more than 64 classes, another
+ * objective, averaged output.  AFX_ERR_INVALID_ARG: text that is no such model (truncated, a list shorter than its count,
+ * an index out of range), a vector value that is not finite, a limit <= 0, early_stop_freq < 1 (INT32_MAX: never stop).
+ * The model holds a reference to the plan, is read-only afterwards and may serve any number of batches of that plan's
+ * device, from any thread. */
+typedef struct afx_model afx_model;
+int afx_model_create_from_lightgbm(afx_plan* plan, const char* const* texts, const size_t* lens, int32_t n_models,
+                                   const double* scale, const double* offset, const double* limits, int32_t early_stop_freq,
+                                   double early_stop_margin, afx_model** out_model);
+void afx_model_destroy(afx_model* model);
+int afx_model_get_info(const afx_model* model, int32_t* n_classes, int32_t* n_models, int32_t* trees_per_model /* [n_models] */);
+/* (any pointer of afx_model_get_info but the model may be NULL)
+ * After afx_batch_run on a batch whose mask holds AFX_D_CLASSIFICATION_INPUTS (otherwise, or before the first run:
+ * AFX_ERR_INVALID_ARG), any number of times.  Synchronous, like the two fetches above: the feature kernel and the models'
+ * kernel on the batch's stream, one transfer of n_classes floats + n_models + 1 integers per file; the features stay on
+ * the device.  A buffer without frames or with a buf_status other than 0 gets zeros.  A buffer with a feature that is NaN
+ * or infinite gets that count in non_finite and a zero signature (the reference fails such a file); every other buffer
+ * count 0.  iterations_used: how many iterations of each model were evaluated before the early stop (all of them when it
+ * never struck; 0 for a buffer that got zeros). */
+int afx_batch_fetch_class_signature(afx_batch* batch, const afx_model* model, float* signature /* [n_bufs][n_classes] */,
+                                    int32_t* iterations_used /* [n_bufs][n_models] or NULL */, int32_t* non_finite /* [n_bufs] or NULL */);
+
+/* The same models on feature vectors the caller holds (a database's rows, vectors written by another program): n_vectors x
+ * AFX_NUM_CLASSIFICATION_FEATURES doubles up, the same kernel, the same three results down.  Not the crawl's path: it
+ * allocates and frees device memory of its own and runs on the device's default stream.  Synchronous.  A vector with a NaN
+ * or an infinity gets its count and zeros, as above. */
+int afx_model_evaluate_features(const afx_model* model, const double* features /* [n_vectors][AFX_NUM_CLASSIFICATION_FEATURES] */,
+                                int32_t n_vectors, float* signature /* [n_vectors][n_classes] */,
+                                int32_t* iterations_used /* [n_vectors][n_models] or NULL */, int32_t* non_finite /* [n_vectors] or NULL */);
 
 /* Page-locked host memory for PCM and result arrays: transfers from / to such buffers run at the
  * host link's rate (pageable memory is staged by the runtime at a fraction of it). */
