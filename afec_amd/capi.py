@@ -66,6 +66,11 @@ D_CLASSIFICATION_INPUTS = (D_MFCC | D_SPECTRAL_RMS | D_SPECTRAL_FLATNESS | D_SPE
                            D_BAND_FEATURES | D_AMPLITUDE_RMS | D_AMPLITUDE_SILENCE | D_SPECTRAL_COMPLEXITY | D_F0 |
                            D_STATISTICS | D_EFFECTIVE_LENGTH | D_RHYTHM)
 CF_TIME_FRAMES, NUM_CLASSIFICATION_FEATURES, NUM_CF_SILENCE = 48, 1680, 21
+# afx_batch_fetch_class_decision: the mask's bits, afx_decision_out.flags, the scalars afx_decide reads per file
+D_CLASS_DECISION_INPUTS = D_CLASSIFICATION_INPUTS | D_AMPLITUDE_PEAK
+DECISION_IS_ONESHOT, DECISION_IS_LOOP, DECISION_OVERRIDDEN = 1, 2, 4
+DECISION_SCALARS = ["effectve_length_24dB", "rhythm_percussive_onset_count", "rhythm_percussive_tempo_confidence",
+                    "rhythm_complex_tempo_confidence", "spectral_flux_mean"]
 PRECISION_F64, PRECISION_F32 = 0, 1
 PCM_F32, PCM_F64 = 0, 1
 FRAME_KERNEL_AUTO, FRAME_KERNEL_WAVE64, FRAME_KERNEL_HALFWAVE = 0, 1, 2   # afx_plan_desc.frame_kernel
@@ -84,7 +89,7 @@ EXPORTS = [
     "afx_batch_fetch_high_level",
     "afx_batch_fetch_classification_features", "afx_classification_feature_name", "afx_plan_get_silence_features",
     "afx_model_create_from_lightgbm", "afx_model_destroy", "afx_model_get_info", "afx_batch_fetch_class_signature",
-    "afx_model_evaluate_features",
+    "afx_model_evaluate_features", "afx_batch_fetch_class_decision", "afx_decide",
 ]
 RAW_I16, RAW_I24, RAW_F32, RAW_I32, RAW_F64 = 0, 1, 2, 3, 4
 
@@ -158,6 +163,26 @@ class _LoadInfo(ctypes.Structure):
 
 class _HighOut(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("scalars", "signature", "pitch", "peak", "status")]
+
+
+class _DecisionDesc(ctypes.Structure):
+    _fields_ = [("class_model", ctypes.c_void_p), ("loop_class", ctypes.c_int32), ("oneshot_class", ctypes.c_int32),
+                ("use_heuristics", ctypes.c_int32), ("category_model", ctypes.c_void_p), ("category_none_class", ctypes.c_int32)]
+
+
+_DECISION_OUT = ("class_signature", "class_strengths", "classes", "category_signature", "category_strengths", "categories",
+                 "confidences", "flags", "non_finite")
+
+
+class _DecisionOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in _DECISION_OUT]
+
+
+class _DecisionIn(ctypes.Structure):
+    _fields_ = [("n_files", ctypes.c_int32), ("n_categories", ctypes.c_int32), ("class_signature", ctypes.c_void_p),
+                ("category_signature", ctypes.c_void_p), ("peaks", ctypes.c_void_p), ("frame_offset", ctypes.c_void_p),
+                ("scalars", ctypes.c_void_p), ("non_finite", ctypes.c_void_p), ("loop_class", ctypes.c_int32),
+                ("oneshot_class", ctypes.c_int32), ("use_heuristics", ctypes.c_int32), ("category_none_class", ctypes.c_int32)]
 
 
 class _StatsOut(ctypes.Structure):
@@ -255,6 +280,8 @@ def load_library():
     L.afx_model_get_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.afx_batch_fetch_class_signature.argtypes = [vp, vp, vp, vp, vp]
     L.afx_model_evaluate_features.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.afx_batch_fetch_class_decision.argtypes = [vp, ctypes.POINTER(_DecisionDesc), ctypes.POINTER(_DecisionOut)]
+    L.afx_decide.argtypes = [vp, ctypes.POINTER(_DecisionIn), ctypes.POINTER(_DecisionOut)]
     _lib = L
     return L
 
@@ -270,6 +297,54 @@ def classification_feature_names():
             _check(L, n)
         names.append(buf.value.decode())
     return names
+
+
+def _decision_out(n, with_classes, k):
+    """the arrays of an afx_decision_out for n files (one spare row for n = 0) -> (struct, dict of [n]-row views)"""
+    rows = max(1, n)
+    arrays = {"confidences": np.zeros((rows, 2)), "flags": np.zeros(rows, dtype=np.int32), "non_finite": np.zeros(rows, dtype=np.int32)}
+    if with_classes:
+        arrays.update(class_signature=np.zeros((rows, 2), dtype=np.float32), class_strengths=np.zeros((rows, 2)),
+                      classes=np.full((rows, 2), -1, dtype=np.int32))
+    if k:
+        arrays.update(category_signature=np.zeros((rows, k), dtype=np.float32), category_strengths=np.zeros((rows, k)),
+                      categories=np.full((rows, k), -1, dtype=np.int32))
+    out = _DecisionOut()
+    for name, a in arrays.items():
+        setattr(out, name, a.ctypes.data)
+    return out, {name: arrays[name][:n] for name in _DECISION_OUT if name in arrays}
+
+
+def decide(plan, peaks, frame_offset, scalars, class_signature=None, category_signature=None, non_finite=None, loop_class=0,
+           oneshot_class=1, use_heuristics=True, category_none_class=-1):
+    """afx_decide: the class decision's kernel (SampleAnalyser.cpp:1097-1231) on inputs of the caller's, no batch: peaks
+    [frame_offset[-1]] (every file's amplitude_peak frames), frame_offset [n + 1], scalars [n][5] (DECISION_SCALARS order),
+    class_signature [n][2] and / or category_signature [n][K] -> dict as Batch.fetch_class_decision's"""
+    frame_offset = np.ascontiguousarray(frame_offset, dtype=np.int64).reshape(-1)
+    n = frame_offset.size - 1
+    peaks = np.ascontiguousarray(peaks, dtype=np.float64).reshape(-1)
+    scalars = np.ascontiguousarray(scalars, dtype=np.float64).reshape(-1, len(DECISION_SCALARS))
+    if n < 0 or scalars.shape[0] != n or (n and peaks.size != frame_offset[-1]):
+        raise ValueError("frame_offset holds n + 1 offsets into peaks, scalars one row per file")
+    d = _DecisionIn(n_files=n, peaks=peaks.ctypes.data, frame_offset=frame_offset.ctypes.data, scalars=scalars.ctypes.data,
+                    loop_class=loop_class, oneshot_class=oneshot_class, use_heuristics=int(bool(use_heuristics)),
+                    category_none_class=category_none_class)
+    k = 0
+    if class_signature is not None:
+        class_signature = np.ascontiguousarray(class_signature, dtype=np.float32).reshape(n, 2)
+        d.class_signature = class_signature.ctypes.data
+    if category_signature is not None:
+        category_signature = np.ascontiguousarray(category_signature, dtype=np.float32)
+        if category_signature.ndim != 2 or category_signature.shape[0] != n:
+            raise ValueError("category_signature holds one row of K weights per file")
+        k = d.n_categories = category_signature.shape[1]
+        d.category_signature = category_signature.ctypes.data
+    if non_finite is not None:
+        non_finite = np.ascontiguousarray(non_finite, dtype=np.int32).reshape(n)
+        d.non_finite = non_finite.ctypes.data
+    out, res = _decision_out(n, class_signature is not None, k)
+    _check(plan.L, plan.L.afx_decide(plan.h, ctypes.byref(d), ctypes.byref(out)))
+    return res
 
 
 def pinned_array(shape, dtype):
@@ -615,6 +690,20 @@ class Batch:
         _check(self.L, self.L.afx_batch_fetch_class_signature(self.h, model.h, signature.ctypes.data, used.ctypes.data,
                                                               non_finite.ctypes.data))
         return signature[:n], used[:n], non_finite[:n]
+
+    def fetch_class_decision(self, class_model=None, category_model=None, loop_class=0, oneshot_class=1, use_heuristics=True,
+                             category_none_class=-1):
+        """afx_batch_fetch_class_decision: what the reference makes of the signatures of every buffer
+        (SampleAnalyser.cpp:1097-1231) -> dict: "confidences" [n][2] (IsOneShot, IsLoop; -1: not evaluated), "flags" [n]
+        (DECISION_*), "non_finite" [n]; with a class model "class_signature" float32 [n][2], "class_strengths" [n][2],
+        "classes" int32 [n][2] (picked indices in pick order, -1 padded); with a category model of K classes
+        "category_signature" [n][K], "category_strengths" [n][K], "categories" [n][K]"""
+        d = _DecisionDesc(class_model=class_model.h if class_model else None, loop_class=loop_class, oneshot_class=oneshot_class,
+                          use_heuristics=int(bool(use_heuristics)), category_model=category_model.h if category_model else None,
+                          category_none_class=category_none_class)
+        out, res = _decision_out(self.n_bufs, class_model is not None, category_model.n_classes if category_model else 0)
+        _check(self.L, self.L.afx_batch_fetch_class_decision(self.h, ctypes.byref(d), ctypes.byref(out)))
+        return res
 
     def close(self):
         if getattr(self, "h", None):

@@ -514,6 +514,82 @@ int afx_model_evaluate_features(const afx_model* model, const double* features /
                                 int32_t n_vectors, float* signature /* [n_vectors][n_classes] */,
                                 int32_t* iterations_used /* [n_vectors][n_models] or NULL */, int32_t* non_finite /* [n_vectors] or NULL */);
 
+/* ---- class decision: what the reference makes of the signatures, SampleAnalyser.cpp:1097-1231 ---- *
+ * The columns a reader of the reference's high-level database sees -- class_strengths, classes, category_signature,
+ * category_strengths, categories -- from the class signature above, formed on the device in the reference's order:
+ *   1. TClassificationTools::CategoryStrengths with MinWeight 0 (ClassificationTools.cpp:7-39): the float signature
+ *      widened to double, divided by its sum in index order; zeros when the sum is not > 0.
+ *   2. TClassificationHeuristics::IsOneShot, and IsLoop when that said no (ClassificationHeuristics.cpp:12-149;
+ *      MUseClassificationHeuristics is defined, SampleAnalyser.cpp:72), on effectve_length_24dB, the amplitude_peak series
+ *      (its frames between the first and the last above -24 dB, correlated with the fade pow(1 - i / (n - 1), 4):
+ *      TStatistics::Correlation, Statistics.cpp:604-638), rhythm_percussive_onset_count, the two tempo confidences and the
+ *      mean of spectral_flux.  A heuristic that says yes against the model overrides the two strengths
+ *      (SampleAnalyser.cpp:1121-1148); they are not renormalised.  use_heuristics == 0 skips this step.
+ *   3. TClassificationTools::PickAllStrongCategories with 0.2 and 0.01 (ClassificationTools.cpp:46-128): repeatedly the
+ *      largest strength above 0.2 not yet picked (of equal ones the later index), else the first maximum if above 0.01; a
+ *      "None" class picked first empties the list, picked later it is removed; the strengths of classes not picked become 0.
+ *      The device works on indices: the caller holds the names and passes the index of "None" (or -1).
+ *   4. The same three steps for the category model when the picked classes are empty or hold oneshot_class; when they hold
+ *      loop_class alone the category strengths are 0 and nothing is picked (the category signature is kept).
+ * A buffer without frames, with a buf_status other than 0, or whose features are not all finite (non_finite != 0: the
+ * reference fails such a file) gets zeros in every output, picks of -1, confidences of -1 and flags 0.
+ * Without a class model (the reference's model "none") the classes are empty, no heuristic runs, and class_signature,
+ * class_strengths and classes are not written; without a category model the three category outputs are not written.
+ * The five sums of the correlation are formed lane-parallel, in another order than the reference's loop: confidences and
+ * strengths agree with a serial evaluation to rounding (about 1e-15 relative), not to the bit. */
+#define AFX_D_CLASS_DECISION_INPUTS (AFX_D_CLASSIFICATION_INPUTS | AFX_D_AMPLITUDE_PEAK)
+enum { AFX_DECISION_IS_ONESHOT = 1, AFX_DECISION_IS_LOOP = 2, AFX_DECISION_OVERRIDDEN = 4 }; /* afx_decision_out.flags */
+typedef struct {
+  const afx_model* class_model;      /* exactly 2 classes (otherwise AFX_ERR_UNSUPPORTED), or NULL: no classes          */
+  int32_t loop_class, oneshot_class; /* 0 and 1 in the reference ("Loop", "OneShot"); distinct, in {0, 1}               */
+  int32_t use_heuristics;            /* 0: the model's strengths go to the pick unchanged                              */
+  const afx_model* category_model;   /* 2..64 classes, or NULL                                                         */
+  int32_t category_none_class;       /* index of the "None" category, or -1                                            */
+} afx_decision_desc;
+typedef struct {                     /* any pointer may be NULL; K = the category model's classes                      */
+  float* class_signature;            /* [n_bufs][2]                                                                    */
+  double* class_strengths;           /* [n_bufs][2], after the override and the pick                                   */
+  int32_t* classes;                  /* [n_bufs][2] picked indices in pick order, -1 padded                            */
+  float* category_signature;         /* [n_bufs][K]                                                                    */
+  double* category_strengths;        /* [n_bufs][K]                                                                    */
+  int32_t* categories;               /* [n_bufs][K] picked indices in pick order, -1 padded                            */
+  double* confidences;               /* [n_bufs][2]: IsOneShot, IsLoop; -1 when not evaluated (as the reference starts) */
+  int32_t* flags;                    /* [n_bufs]: AFX_DECISION_*                                                       */
+  int32_t* non_finite;               /* [n_bufs]: as afx_batch_fetch_class_signature reports it                        */
+} afx_decision_out;
+/* After afx_batch_run on a batch whose mask holds AFX_D_CLASS_DECISION_INPUTS, any number of times.  Synchronous, on the
+ * batch's stream: the feature kernel once, the models' kernel once per model given, the decision kernel; one transfer brings
+ * back the outputs only.  AFX_ERR_INVALID_ARG: before the first run, a mask that lacks an input, both models NULL, a model
+ * on another device, loop_class / oneshot_class not 0 and 1, category_none_class outside -1..K-1.  AFX_ERR_UNSUPPORTED: a
+ * class model with another number of classes than 2. */
+int afx_batch_fetch_class_decision(afx_batch* batch, const afx_decision_desc* desc, afx_decision_out* out);
+
+/* The same kernel on inputs the caller holds (a database's rows re-decided under another model, or without heuristics):
+ * the signatures as floats, every file's amplitude_peak frames behind one another with their offsets, and five scalars per
+ * file.  Not the crawl's path: it allocates and frees device memory of its own on the plan's device and runs on the device's
+ * default stream.  Synchronous.  The signatures come back in `out` as they went in.  AFX_ERR_INVALID_ARG: both signatures
+ * NULL, n_categories outside 2..64, indices as above, frame_offset that does not start at 0 or steps back. */
+#define AFX_NUM_DECISION_SCALARS 5
+enum {
+  AFX_DS_EFFECTIVE_LENGTH_24DB = 0,      /* effectve_length_24dB, seconds        */
+  AFX_DS_PERCUSSIVE_ONSET_COUNT,         /* rhythm_percussive_onset_count        */
+  AFX_DS_PERCUSSIVE_TEMPO_CONFIDENCE,    /* rhythm_percussive_tempo_confidence   */
+  AFX_DS_COMPLEX_TEMPO_CONFIDENCE,       /* rhythm_complex_tempo_confidence      */
+  AFX_DS_SPECTRAL_FLUX_MEAN              /* the mean of spectral_flux            */
+};
+typedef struct {
+  int32_t n_files;
+  int32_t n_categories;                  /* K: 2..64 with a category signature                                        */
+  const float* class_signature;          /* [n_files][2], or NULL: no classes                                         */
+  const float* category_signature;       /* [n_files][K], or NULL                                                     */
+  const double* peaks;                   /* [frame_offset[n_files]]: amplitude_peak, file after file                  */
+  const int64_t* frame_offset;           /* [n_files + 1]                                                             */
+  const double* scalars;                 /* [n_files][AFX_NUM_DECISION_SCALARS], AFX_DS_* order                       */
+  const int32_t* non_finite;             /* [n_files], or NULL: all 0                                                 */
+  int32_t loop_class, oneshot_class, use_heuristics, category_none_class; /* as afx_decision_desc                      */
+} afx_decision_in;
+int afx_decide(const afx_plan* plan, const afx_decision_in* in, afx_decision_out* out);
+
 /* Page-locked host memory for PCM and result arrays: transfers from / to such buffers run at the
  * host link's rate (pageable memory is staged by the runtime at a fraction of it). */
 void* afx_host_alloc(int64_t bytes);
