@@ -33,6 +33,13 @@ int effective_length_seconds(afx_batch* b, double* seconds) {
 }  // namespace host
 }  // namespace afx
 
+namespace {
+
+// one series of a fetch: where the caller wants it, where it lies in a record, how wide it is
+struct Field { double* dst; int32_t off; int width; };
+
+}  // namespace
+
 extern "C" {
 
 int afx_batch_fetch_samples(afx_batch* b, int32_t buf, double* dst, int64_t n) {
@@ -94,12 +101,8 @@ int afx_batch_fetch(afx_batch* b, afx_out* out) {
   const int64_t F = b->total_frames;
   if (F == 0) return AFX_OK;
   const afx::RecordLayout& l = b->lay;
-  struct Field { double* dst; int32_t off; int width; };
   std::vector<Field> fields;
   for (const FieldDesc& d : kFields) fields.push_back(Field{out->*(d.out), l.*(d.off), d.width});
-  for (const Field& f : fields)
-    if (f.dst && f.off < 0) return fail(AFX_ERR_INVALID_ARG, "output requested that is not in the batch mask");
-  if (out->magnitude && !(b->mask & AFX_D_MAGNITUDE)) return fail(AFX_ERR_INVALID_ARG, "magnitude not in the batch mask");
   bool any_series = false;
   for (const Field& f : fields) any_series = any_series || f.dst != nullptr;
   if (l.stride > 0 && any_series) {
@@ -124,17 +127,16 @@ int afx_batch_fetch_statistics(afx_batch* b, afx_stats_out* out) {
   HIP_TRY(hipSetDevice(b->plan->desc.device));
   HIP_TRY(hipStreamSynchronize(b->stream));
   const afx::RecordLayout& l = b->lay;
-  std::vector<double> st((size_t)b->n_bufs * l.stride * 13);
+  std::vector<double> st((size_t)b->n_bufs * l.stride * AFX_NUM_STATISTICS);
   HIP_TRY(hipMemcpy(st.data(), b->d_stats, st.size() * sizeof(double), hipMemcpyDeviceToHost));
-  struct Field { double* dst; int32_t off; int width; };
   std::vector<Field> fields;
   for (const FieldDesc& d : kFields) fields.push_back(Field{out->*(d.stat), l.*(d.off), d.width});
   for (const Field& f : fields) {
     if (!f.dst) continue;
     if (f.off < 0) return fail(AFX_ERR_INVALID_ARG, "statistics requested for a series that is not in the batch mask");
     for (int32_t i = 0; i < b->n_bufs; ++i)
-      std::memcpy(f.dst + (size_t)i * f.width * 13, st.data() + ((size_t)i * l.stride + f.off) * 13,
-                  (size_t)f.width * 13 * sizeof(double));
+      std::memcpy(f.dst + (size_t)i * f.width * AFX_NUM_STATISTICS, st.data() + ((size_t)i * l.stride + f.off) * AFX_NUM_STATISTICS,
+                  (size_t)f.width * AFX_NUM_STATISTICS * sizeof(double));
   }
   if (out->stats_status)
     for (int32_t i = 0; i < b->n_bufs; ++i) {
@@ -162,7 +164,7 @@ int afx_batch_fetch_records(afx_batch* b, double* records, double* statistics, i
   if (statistics && !b->d_stats && b->n_bufs > 0) return fail(AFX_ERR_INVALID_ARG, "AFX_D_STATISTICS was not in the batch mask");
   HIP_TRY(hipSetDevice(b->plan->desc.device));
   const size_t rec_bytes = (size_t)b->total_frames * b->lay.stride * sizeof(double);
-  const size_t stat_bytes = (size_t)b->n_bufs * b->lay.stride * 13 * sizeof(double);
+  const size_t stat_bytes = (size_t)b->n_bufs * b->lay.stride * AFX_NUM_STATISTICS * sizeof(double);
   {
     const Download items[2] = {{records, b->d_rec, rec_bytes}, {statistics, b->d_stats, stat_bytes}};
     HIP_TRY(download_through_plan(b, items, 2));
@@ -170,9 +172,7 @@ int afx_batch_fetch_records(afx_batch* b, double* records, double* statistics, i
   if (frame_offset) std::memcpy(frame_offset, b->frame_offset.data(), b->frame_offset.size() * sizeof(int64_t));
   if (buf_status) std::memcpy(buf_status, b->buf_status.data(), b->buf_status.size() * sizeof(int32_t));
   if (effective_length) {
-    afx_out tmp = {};
-    tmp.effective_length = effective_length;
-    const int st = afx_batch_fetch(b, &tmp);
+    const int st = effective_length_seconds(b, effective_length);   // the stream is idle behind download_through_plan
     if (st != AFX_OK) return st;
   }
   return AFX_OK;
@@ -211,7 +211,7 @@ int afx_batch_fetch_rhythm(afx_batch* b, double* onsets, double* scalars, double
   {
     const Download items[3] = {{onsets, b->d_rt_onsets, rows * 2 * sizeof(double)},
                                {scalars, b->d_rt_scalars, (size_t)b->n_bufs * AFX_NUM_RHYTHM_SCALARS * sizeof(double)},
-                               {onset_statistics, b->d_rt_stats, (size_t)b->n_bufs * 2 * 13 * sizeof(double)}};
+                               {onset_statistics, b->d_rt_stats, (size_t)b->n_bufs * 2 * AFX_NUM_STATISTICS * sizeof(double)}};
     HIP_TRY(download_through_plan(b, items, 3));
   }
   return AFX_OK;

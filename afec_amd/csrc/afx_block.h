@@ -1,0 +1,129 @@
+// afec_amd/csrc/afx_block.h -- how the fetches above a run (afx_high_level.cpp, afx_classification.cpp,
+// afx_class_decision.cpp) lay out memory, host only.  A block holds typed arrays behind one another, the same way on the
+// device and on the host, so that one transfer moves a run of them.  Layout hands out the offsets and is the only place a
+// byte offset is formed; each fetch names its block once as a struct of offsets with point() (the kernel's arguments into a
+// block at `base`) and hand_out() (the host copy into the caller's arrays).  ResultBlock is the batch's reused block behind
+// the checks every such fetch starts with, DeviceBlock the memory of an entry point that has no batch.
+#pragma once
+
+#include <cstring>
+
+#include "afx_host.h"
+#include "classify/afx_classify.h"
+
+namespace afx {
+namespace host {
+
+// Every array starts at a multiple of 8 bytes, the alignment of the widest type a block holds: an odd number of int32 or
+// float in front of doubles costs four bytes, and any array's offset is a place where a transfer may start or end.
+class Layout {
+ public:
+  template <typename T>
+  size_t take(size_t count) {
+    static_assert(alignof(T) <= 8, "a block is aligned for doubles");
+    const size_t at = bytes_;
+    bytes_ = (at + count * sizeof(T) + 7) & ~(size_t)7;
+    return at;
+  }
+  size_t bytes() const { return bytes_; }   // so far: where the next array will start
+
+ private:
+  size_t bytes_ = 0;
+};
+
+template <typename T>
+T* at(char* base, size_t offset) { return reinterpret_cast<T*>(base + offset); }
+template <typename T>
+const T* at(const char* base, size_t offset) { return reinterpret_cast<const T*>(base + offset); }
+
+// The workspace's result buffer on the device and the page-locked one it lands in, reserved for one fetch's layout (the
+// fetches are synchronous: one at a time uses them).  n: the batch's buffers; 0: nothing reserved, nothing to launch.
+struct ResultBlock {
+  size_t n = 0;
+  char *dev = nullptr, *host = nullptr;
+};
+
+#define AFX_TRY(expr)                   \
+  do {                                  \
+    const int st_ = (expr);             \
+    if (st_ != AFX_OK) return st_;      \
+  } while (0)
+
+// What every fetch above a run starts with.  `has_inputs`: the batch's mask holds what the fetch reads (`lacks` is the
+// text when not); `who` names the entry point for "... before afx_batch_run".  AFX_OK with rb->n == 0: an empty batch.
+inline int reserve_result_block(afx_batch* b, bool has_inputs, const char* lacks, const char* who, const Layout& layout, ResultBlock* rb) {
+  if (!has_inputs) return fail(AFX_ERR_INVALID_ARG, lacks);
+  if (!b->ran) return fail(AFX_ERR_INVALID_ARG, std::string(who) + " before afx_batch_run");
+  if (b->n_bufs == 0) return AFX_OK;
+  HIP_TRY(hipSetDevice(b->plan->desc.device));
+  HIP_TRY(ws_reserve(b->plan, b->ws->high, layout.bytes()));
+  HIP_TRY(ws_result_pin_reserve(b->ws, layout.bytes()));
+  rb->n = (size_t)b->n_bufs;
+  rb->dev = (char*)b->ws->high.p;
+  rb->host = (char*)b->ws->h_high;
+  return AFX_OK;
+}
+
+// [from, to) of the block from the device to the host: waits for the batch's stream first, then for the transfer
+inline hipError_t download_result(afx_batch* b, const ResultBlock& rb, size_t from, size_t to) {
+  const Download item{rb.host + from, rb.dev + from, to - from};
+  return download_through_plan(b, &item, 1);
+}
+
+// Device memory of a call's own, freed when it leaves scope.
+class DeviceBlock {
+ public:
+  DeviceBlock() = default;
+  DeviceBlock(const DeviceBlock&) = delete;
+  DeviceBlock& operator=(const DeviceBlock&) = delete;
+  ~DeviceBlock() {
+    if (p_) (void)hipFree(p_);
+  }
+  int allocate(size_t bytes, const char* what) {   // `what`: the text of AFX_ERR_OUT_OF_MEMORY
+    const hipError_t e = hipMalloc(&p_, bytes);
+    if (e == hipSuccess) return AFX_OK;
+    p_ = nullptr;
+    if (e == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      return fail(AFX_ERR_OUT_OF_MEMORY, what);
+    }
+    return hip_fail(e, "hipMalloc");
+  }
+  char* get() const { return (char*)p_; }
+
+ private:
+  void* p_ = nullptr;
+};
+
+// What classification_features_kernel writes and the feature fetch brings back (features, counts), then what goes up for it
+// in one transfer: effectve_length_12dB for the features, effectve_length_24dB for the class decision's heuristics, the
+// buffers' status.  A fetch that runs kernels of its own on the features takes its arrays from the same Layout behind it.
+struct FeatureBlock {
+  size_t n, features, non_finite, efflen12, efflen24, status, end;
+  FeatureBlock(Layout& l, size_t n_bufs) : n(n_bufs) {
+    features = l.take<double>(n * kClassifyFeatures);
+    non_finite = l.take<int32_t>(n);
+    efflen12 = l.take<double>(n);
+    efflen24 = l.take<double>(n);
+    status = l.take<int32_t>(n);
+    end = l.bytes();
+  }
+  void point(ClassifyArgs* a, char* base) const {
+    a->features = at<double>(base, features);
+    a->non_finite = at<int32_t>(base, non_finite);
+    a->efflen12 = at<double>(base, efflen12);
+    a->status = at<int32_t>(base, status);
+  }
+  void hand_out(const char* host, double* out_features, int32_t* out_non_finite) const {
+    std::memcpy(out_features, host + features, n * kClassifyFeatures * sizeof(double));
+    if (out_non_finite) std::memcpy(out_non_finite, host + non_finite, n * sizeof(int32_t));
+  }
+};
+
+// afx_classification.cpp: the launch the three batch fetches of the features share.  Reserves the batch's result block for
+// `layout` (which starts with `fb`), uploads the kernel's small inputs and launches it, all on the batch's stream; nothing
+// is downloaded and nothing waited for behind the launch.  rb->n == 0: an empty batch, nothing launched.
+int launch_features(afx_batch* b, const char* who, const Layout& layout, const FeatureBlock& fb, ResultBlock* rb);
+
+}  // namespace host
+}  // namespace afx

@@ -1,0 +1,282 @@
+// afec_amd/csrc/afx_class_decision.cpp -- the fetches that evaluate the reference's models on the classification features.
+// afx_batch_fetch_class_signature shares the feature fetch's launch (launch_features, afx_classification.cpp): the same
+// kernel into the same block, the models' kernel (gbdt/afx_gbdt.hip) behind it on the same stream, and only that kernel's
+// few bytes per file come back (SampleAnalyser.cpp:1075-1231).  afx_batch_fetch_class_decision goes one kernel further
+// (decide/afx_decide.hip): what the reference makes of the signatures -- strengths, heuristics, classes, categories
+// (SampleAnalyser.cpp:1097-1231).  afx_model_evaluate_features and afx_decide run the same two kernels on inputs the caller
+// holds, in a device block of their own.  Every entry point reads: check, layout, arguments, launch, one download, hand out.
+
+#include <cmath>
+#include <cstring>
+
+#include "afx_block.h"
+#include "afx_model.h"
+#include "decide/afx_decide.h"
+#include "gbdt/afx_gbdt.h"
+
+using namespace afx::host;
+
+namespace {
+
+// What class_signature_kernel writes for one bagging, and what a signature fetch brings back.
+struct SignatureBlock {
+  size_t n, n_classes, n_models, signature, iterations_used, non_finite, end;
+  SignatureBlock(Layout& l, size_t n_vectors, const afx::GbdtModel& m) : n(n_vectors), n_classes((size_t)m.n_classes), n_models((size_t)m.n_models) {
+    signature = l.take<float>(n * n_classes);
+    iterations_used = l.take<int32_t>(n * n_models);
+    non_finite = l.take<int32_t>(n);
+    end = l.bytes();
+  }
+  void hand_out(const char* host, float* out_signature, int32_t* out_iterations_used, int32_t* out_non_finite) const {
+    std::memcpy(out_signature, host + signature, n * n_classes * sizeof(float));
+    if (out_iterations_used) std::memcpy(out_iterations_used, host + iterations_used, n * n_models * sizeof(int32_t));
+    if (out_non_finite) std::memcpy(out_non_finite, host + non_finite, n * sizeof(int32_t));
+  }
+};
+
+// one launch of the models' kernel: `n` vectors at `features` of a block at `base`, its three results at the offsets given
+afx::GbdtArgs gbdt_args(const afx_model* model, char* base, size_t features, const int64_t* frame_offset, size_t status, int32_t n,
+                        size_t signature, size_t iterations_used, size_t non_finite) {
+  afx::GbdtArgs g{};
+  g.model = model->dev;
+  g.features = at<double>(base, features);
+  g.frame_offset = frame_offset;
+  g.status = at<int32_t>(base, status);
+  g.n_bufs = n;
+  g.signature = at<float>(base, signature);
+  g.iterations_used = at<int32_t>(base, iterations_used);
+  g.non_finite = at<int32_t>(base, non_finite);
+  return g;
+}
+
+// What afx_decision_out names: the two signatures (a model that is not there has an array of no length), which the decision
+// kernel reads, then what it writes.
+struct DecisionBlock {
+  size_t n, k, signature[2], class_strengths, confidences, category_strengths, classes, categories, flags, non_finite, end;
+  bool with_classes;
+  DecisionBlock(Layout& l, size_t n_files, bool has_class_model, size_t n_categories) : n(n_files), k(n_categories), with_classes(has_class_model) {
+    signature[0] = l.take<float>(with_classes ? n * 2 : 0);
+    signature[1] = l.take<float>(n * k);
+    class_strengths = l.take<double>(n * 2);
+    confidences = l.take<double>(n * 2);
+    category_strengths = l.take<double>(n * k);
+    classes = l.take<int32_t>(n * 2);
+    categories = l.take<int32_t>(n * k);
+    flags = l.take<int32_t>(n);
+    non_finite = l.take<int32_t>(n);
+    end = l.bytes();
+  }
+  void point(afx::DecideArgs* a, char* base) const {
+    a->class_signature = with_classes ? at<float>(base, signature[0]) : nullptr;
+    a->category_signature = k ? at<float>(base, signature[1]) : nullptr;
+    a->class_strengths = at<double>(base, class_strengths);
+    a->confidences = at<double>(base, confidences);
+    a->category_strengths = at<double>(base, category_strengths);
+    a->classes = at<int32_t>(base, classes);
+    a->categories = at<int32_t>(base, categories);
+    a->flags = at<int32_t>(base, flags);
+    a->non_finite = at<int32_t>(base, non_finite);
+  }
+  void hand_out(const char* host, afx_decision_out* out) const {
+    // without a class model the reference's lists are empty: nothing is written for them
+    if (out->class_signature && with_classes) std::memcpy(out->class_signature, host + signature[0], n * 2 * sizeof(float));
+    if (out->class_strengths && with_classes) std::memcpy(out->class_strengths, host + class_strengths, n * 2 * sizeof(double));
+    if (out->classes && with_classes) std::memcpy(out->classes, host + classes, n * 2 * sizeof(int32_t));
+    if (out->category_signature && k) std::memcpy(out->category_signature, host + signature[1], n * k * sizeof(float));
+    if (out->category_strengths && k) std::memcpy(out->category_strengths, host + category_strengths, n * k * sizeof(double));
+    if (out->categories && k) std::memcpy(out->categories, host + categories, n * k * sizeof(int32_t));
+    if (out->confidences) std::memcpy(out->confidences, host + confidences, n * 2 * sizeof(double));
+    if (out->flags) std::memcpy(out->flags, host + flags, n * sizeof(int32_t));
+    if (out->non_finite) std::memcpy(out->non_finite, host + non_finite, n * sizeof(int32_t));
+  }
+};
+
+// Between the feature block and the decision block of a batch's class decision: what the models' kernel writes and only the
+// decision kernel reads, for the class model [0] and the category model [1].  It stays on the device.
+struct DecisionScratch {
+  size_t iterations_used[2], non_finite[2];
+  DecisionScratch(Layout& l, size_t n, const afx_model* const models[2]) {
+    for (int m = 0; m < 2; ++m) iterations_used[m] = l.take<int32_t>(models[m] ? n * (size_t)models[m]->dev.n_models : 0);
+    for (int m = 0; m < 2; ++m) non_finite[m] = l.take<int32_t>(n);
+  }
+};
+
+// What goes up for afx_decide in front of its decision block.
+struct DecideInputs {
+  size_t n, frames, peaks, scalars, frame_offset, non_finite;
+  DecideInputs(Layout& l, const afx_decision_in* in) : n((size_t)in->n_files), frames((size_t)in->frame_offset[in->n_files]) {
+    peaks = l.take<double>(frames);
+    scalars = l.take<double>(n * AFX_NUM_DECISION_SCALARS);
+    frame_offset = l.take<int64_t>(n + 1);
+    non_finite = l.take<int32_t>(n);
+  }
+  void fill(char* host, const afx_decision_in* in) const {   // `host` starts out as zeros: a count that is not given is 0
+    if (frames) std::memcpy(host + peaks, in->peaks, frames * sizeof(double));
+    std::memcpy(host + scalars, in->scalars, n * AFX_NUM_DECISION_SCALARS * sizeof(double));
+    std::memcpy(host + frame_offset, in->frame_offset, (n + 1) * sizeof(int64_t));
+    if (in->non_finite) std::memcpy(host + non_finite, in->non_finite, n * sizeof(int32_t));
+  }
+  void point(afx::DecideArgs* a, char* base) const {
+    const double* const s = at<double>(base, scalars);
+    a->peak = at<double>(base, peaks);
+    a->peak_stride = 1;
+    a->frame_offset = at<int64_t>(base, frame_offset);
+    a->efflen24 = {s + AFX_DS_EFFECTIVE_LENGTH_24DB, AFX_NUM_DECISION_SCALARS};
+    a->onset_count = {s + AFX_DS_PERCUSSIVE_ONSET_COUNT, AFX_NUM_DECISION_SCALARS};
+    a->percussive_confidence = {s + AFX_DS_PERCUSSIVE_TEMPO_CONFIDENCE, AFX_NUM_DECISION_SCALARS};
+    a->complex_confidence = {s + AFX_DS_COMPLEX_TEMPO_CONFIDENCE, AFX_NUM_DECISION_SCALARS};
+    a->flux_mean = {s + AFX_DS_SPECTRAL_FLUX_MEAN, AFX_NUM_DECISION_SCALARS};
+    a->status = nullptr;
+    a->non_finite_in = at<int32_t>(base, non_finite);
+  }
+};
+
+// the indices a decision names: AFX_OK or why not
+int check_decision_indices(int loop_class, int oneshot_class, int none_class, int n_categories) {
+  if (loop_class < 0 || loop_class > 1 || oneshot_class < 0 || oneshot_class > 1 || loop_class == oneshot_class)
+    return fail(AFX_ERR_INVALID_ARG, "loop_class and oneshot_class are 0 and 1 in either order");
+  if (none_class < -1 || none_class >= n_categories) return fail(AFX_ERR_INVALID_ARG, "category_none_class names no class of the category model");
+  return AFX_OK;
+}
+
+// what a decision is told, the same from a batch and from the caller's arrays; the blocks point the rest
+afx::DecideArgs decide_args(int32_t n_files, size_t n_categories, int loop_class, int oneshot_class, int use_heuristics, int none_class) {
+  afx::DecideArgs a{};
+  a.n_categories = (int32_t)n_categories;
+  a.loop_class = loop_class;
+  a.oneshot_class = oneshot_class;
+  a.use_heuristics = use_heuristics != 0;
+  a.none_category = none_class;
+  a.silence_floor = std::exp(-24.0 * (std::log(10.0) / 20.0));   // DbToLin(-24), AudioMath.inl:108-123
+  a.n_files = n_files;
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int afx_batch_fetch_class_signature(afx_batch* b, const afx_model* model, float* signature, int32_t* iterations_used, int32_t* nonfinite) {
+  if (!b || !model || !signature) return fail(AFX_ERR_INVALID_ARG, "null argument");
+  if (model->plan->desc.device != b->plan->desc.device) return fail(AFX_ERR_INVALID_ARG, "the model lives on another device than the batch");
+  Layout layout;
+  const FeatureBlock fb(layout, (size_t)b->n_bufs);
+  const SignatureBlock sb(layout, (size_t)b->n_bufs, model->dev);
+  ResultBlock rb;
+  const int st = launch_features(b, "afx_batch_fetch_class_signature", layout, fb, &rb);
+  if (st != AFX_OK || rb.n == 0) return st;
+  const afx::GbdtArgs g = gbdt_args(model, rb.dev, fb.features, b->d_frame_offset, fb.status, b->n_bufs, sb.signature, sb.iterations_used, sb.non_finite);
+  HIP_TRY(afx::launch_class_signature(g, b->stream));
+  HIP_TRY(download_result(b, rb, sb.signature, sb.end));
+  sb.hand_out(rb.host, signature, iterations_used, nonfinite);
+  return AFX_OK;
+}
+
+int afx_model_evaluate_features(const afx_model* model, const double* features, int32_t n_vectors, float* signature,
+                                int32_t* iterations_used, int32_t* nonfinite) {
+  if (!model || n_vectors < 0 || (n_vectors > 0 && (!features || !signature))) return fail(AFX_ERR_INVALID_ARG, "bad argument");
+  if (n_vectors == 0) return AFX_OK;
+  HIP_TRY(hipSetDevice(model->plan->desc.device));
+  // one block of its own (this is not the crawl's path: no batch, no workspace): a frame table that gives every vector one
+  // frame and a status of zeros, what the kernel writes, and last the vectors, which go up from the caller's own array
+  const size_t n = (size_t)n_vectors;
+  Layout layout;
+  const size_t frame_offset = layout.take<int64_t>(n + 1), status = layout.take<int32_t>(n);
+  const SignatureBlock sb(layout, n, model->dev);
+  const size_t vectors = layout.take<double>(n * afx::kGbdtFeatures);
+  std::vector<char> host(vectors, 0);
+  for (size_t i = 0; i <= n; ++i) at<int64_t>(host.data(), frame_offset)[i] = (int64_t)i;
+  DeviceBlock dev;
+  AFX_TRY(dev.allocate(layout.bytes(), "device memory for the feature vectors"));
+  const afx::GbdtArgs g = gbdt_args(model, dev.get(), vectors, at<int64_t>(dev.get(), frame_offset), status, n_vectors, sb.signature,
+                                    sb.iterations_used, sb.non_finite);
+  HIP_TRY(hipMemcpy(dev.get() + vectors, features, layout.bytes() - vectors, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dev.get(), host.data(), sb.signature, hipMemcpyHostToDevice));
+  HIP_TRY(afx::launch_class_signature(g, nullptr));
+  HIP_TRY(hipMemcpy(host.data() + sb.signature, dev.get() + sb.signature, sb.end - sb.signature, hipMemcpyDeviceToHost));   // waits for the kernel
+  sb.hand_out(host.data(), signature, iterations_used, nonfinite);
+  return AFX_OK;
+}
+
+int afx_batch_fetch_class_decision(afx_batch* b, const afx_decision_desc* desc, afx_decision_out* out) {
+  if (!b || !desc || !out) return fail(AFX_ERR_INVALID_ARG, "null argument");
+  const afx_model* const models[2] = {desc->class_model, desc->category_model};
+  if (!models[0] && !models[1]) return fail(AFX_ERR_INVALID_ARG, "neither a class model nor a category model");
+  for (const afx_model* m : models)
+    if (m && m->plan->desc.device != b->plan->desc.device) return fail(AFX_ERR_INVALID_ARG, "a model lives on another device than the batch");
+  if (models[0] && models[0]->dev.n_classes != afx::kDecideClasses)
+    return fail(AFX_ERR_UNSUPPORTED, "the class model has to have the two classes \"Loop\" and \"OneShot\"");
+  const size_t k = models[1] ? (size_t)models[1]->dev.n_classes : 0;
+  AFX_TRY(check_decision_indices(desc->loop_class, desc->oneshot_class, desc->category_none_class, (int)k));
+  if (!(b->mask & AFX_D_AMPLITUDE_PEAK)) return fail(AFX_ERR_INVALID_ARG, "the batch mask lacks AFX_D_AMPLITUDE_PEAK (AFX_D_CLASS_DECISION_INPUTS)");
+  Layout layout;
+  const FeatureBlock fb(layout, (size_t)b->n_bufs);
+  const DecisionScratch scratch(layout, (size_t)b->n_bufs, models);
+  const DecisionBlock db(layout, (size_t)b->n_bufs, models[0] != nullptr, k);
+  ResultBlock rb;
+  const int st = launch_features(b, "afx_batch_fetch_class_decision", layout, fb, &rb);
+  if (st != AFX_OK || rb.n == 0) return st;
+
+  for (int m = 0; m < 2; ++m) {
+    if (!models[m]) continue;
+    const afx::GbdtArgs g = gbdt_args(models[m], rb.dev, fb.features, b->d_frame_offset, fb.status, b->n_bufs, db.signature[m],
+                                      scratch.iterations_used[m], scratch.non_finite[m]);
+    HIP_TRY(afx::launch_class_signature(g, b->stream));
+  }
+  afx::DecideArgs a = decide_args(b->n_bufs, k, desc->loop_class, desc->oneshot_class, desc->use_heuristics, desc->category_none_class);
+  a.peak = b->d_rec + b->lay.amp_peak;
+  a.peak_stride = b->lay.stride;
+  a.frame_offset = b->d_frame_offset;
+  a.efflen24 = {at<double>(rb.dev, fb.efflen24), 1};
+  a.onset_count = {b->d_rt_scalars + AFX_R_PERCUSSIVE_ONSET_COUNT, AFX_NUM_RHYTHM_SCALARS};
+  a.percussive_confidence = {b->d_rt_scalars + AFX_R_PERCUSSIVE_TEMPO_CONFIDENCE, AFX_NUM_RHYTHM_SCALARS};
+  a.complex_confidence = {b->d_rt_scalars + AFX_R_COMPLEX_TEMPO_CONFIDENCE, AFX_NUM_RHYTHM_SCALARS};
+  a.flux_mean = {b->d_stats + (size_t)b->lay.flux * AFX_NUM_STATISTICS + AFX_S_MEAN, (int64_t)b->lay.stride * AFX_NUM_STATISTICS};
+  a.status = at<int32_t>(rb.dev, fb.status);
+  // the same features: the same count from either model's kernel
+  a.non_finite_in = at<int32_t>(rb.dev, scratch.non_finite[models[0] ? 0 : 1]);
+  db.point(&a, rb.dev);
+  HIP_TRY(afx::launch_class_decision(a, b->stream));
+  HIP_TRY(download_result(b, rb, db.signature[0], db.end));
+  db.hand_out(rb.host, out);
+  return AFX_OK;
+}
+
+int afx_decide(const afx_plan* plan, const afx_decision_in* in, afx_decision_out* out) {
+  if (!plan || !in || !out || in->n_files < 0) return fail(AFX_ERR_INVALID_ARG, "bad argument");
+  const bool with_classes = in->class_signature != nullptr, with_categories = in->category_signature != nullptr;
+  if (!with_classes && !with_categories) return fail(AFX_ERR_INVALID_ARG, "neither a class signature nor a category signature");
+  if (with_categories && (in->n_categories < 2 || in->n_categories > afx::kDecideMaxCategories))
+    return fail(AFX_ERR_INVALID_ARG, "n_categories outside 2..64");
+  const size_t n = (size_t)in->n_files, k = with_categories ? (size_t)in->n_categories : 0;
+  AFX_TRY(check_decision_indices(in->loop_class, in->oneshot_class, in->category_none_class, (int)k));
+  if (n == 0) return AFX_OK;
+  if (!in->frame_offset || !in->scalars) return fail(AFX_ERR_INVALID_ARG, "null argument");
+  // the kernel follows these offsets into the peaks: they start at 0 and never step back
+  if (in->frame_offset[0] != 0) return fail(AFX_ERR_INVALID_ARG, "frame_offset[0] is not 0");
+  for (size_t i = 0; i < n; ++i)
+    if (in->frame_offset[i + 1] < in->frame_offset[i]) return fail(AFX_ERR_INVALID_ARG, "frame_offset steps back");
+  if (in->frame_offset[n] > 0 && !in->peaks) return fail(AFX_ERR_INVALID_ARG, "null argument");
+  HIP_TRY(hipSetDevice(plan->desc.device));
+  // one block of its own (this is not the crawl's path: no batch, no workspace): what goes up -- the inputs and the decision
+  // block's signatures -- then what the kernel writes
+  Layout layout;
+  const DecideInputs inputs(layout, in);
+  const DecisionBlock db(layout, n, with_classes, k);
+  std::vector<char> host(layout.bytes(), 0);
+  inputs.fill(host.data(), in);
+  if (with_classes) std::memcpy(host.data() + db.signature[0], in->class_signature, n * 2 * sizeof(float));
+  if (with_categories) std::memcpy(host.data() + db.signature[1], in->category_signature, n * k * sizeof(float));
+  DeviceBlock dev;
+  AFX_TRY(dev.allocate(layout.bytes(), "device memory for the decision's inputs"));
+  afx::DecideArgs a = decide_args(in->n_files, k, in->loop_class, in->oneshot_class, in->use_heuristics, in->category_none_class);
+  inputs.point(&a, dev.get());
+  db.point(&a, dev.get());
+  HIP_TRY(hipMemcpy(dev.get(), host.data(), db.class_strengths, hipMemcpyHostToDevice));
+  HIP_TRY(afx::launch_class_decision(a, nullptr));
+  HIP_TRY(hipMemcpy(host.data() + db.class_strengths, dev.get() + db.class_strengths, db.end - db.class_strengths, hipMemcpyDeviceToHost));   // waits for the kernel
+  db.hand_out(host.data(), out);   // the signatures as they went in
+  return AFX_OK;
+}
+
+}  // extern "C"

@@ -11,13 +11,17 @@
 //                       afx_extract_batch
 //   afx_batch_run.cpp   afx_batch_run: the kernels of one pass in stream order (SampleAnalyser.cpp:814-1048)
 //   afx_batch_fetch.cpp results back to the host, batch information, afx_batch_destroy
+//   afx_block.h         how the fetches above a run lay out a block of memory: Layout, the batch's result block, a
+//                       device block of a call's own (host only; the three files below use it)
 //   afx_high_level.cpp  afx_batch_fetch_high_level (SampleAnalyser.cpp:1234-1606); its launcher is declared in
 //                       highlevel/afx_highlevel.h, and none of the files above refers to either
 //   afx_classification.cpp  afx_batch_fetch_classification_features (SampleClassificationDescriptors.cpp:395-561), the
-//                       features' names and silence values; its launcher is declared in classify/afx_classify.h.
-//                       afx_batch_fetch_class_signature beside it (the same launch, then gbdt/afx_gbdt.h's)
+//                       features' names and silence values; its launcher is declared in classify/afx_classify.h
+//   afx_class_decision.cpp  the fetches that evaluate models on those features: afx_batch_fetch_class_signature (the same
+//                       launch, then gbdt/afx_gbdt.h's), afx_batch_fetch_class_decision (then decide/afx_decide.h's), and
+//                       the two on the caller's own arrays, afx_model_evaluate_features and afx_decide
 //   afx_model.cpp       afx_model_create_from_lightgbm / _get_info / _destroy: LightGBM's text into the arrays of
-//                       gbdt/afx_gbdt.h (afx_model.h); no launch, so it links against the device mock as it is
+//                       gbdt/afx_gbdt.h (afx_model.h); no launch
 //
 // Nothing here computes a descriptor: every kernel lives in the .hip files (afx_internal.h declares their launchers).
 #pragma once
@@ -141,7 +145,7 @@ struct Workspace {
   Buf rt_odf, rt_onsets, rt_scratch, rt_scalars, rt_stats, rt_polar;   // rhythm tracker (its host-filled tables lie in `tables`)
   Buf stat_tmp;                                                                 // half-wave statistics class
   Buf rs_files, rs_groups, rs_ngroups;                                          // sample-rate conversion (afx_resample.hip)
-  Buf high;                       // the result block of afx_batch_fetch_high_level / afx_batch_fetch_classification_features (one at a time: both are synchronous)
+  Buf high;                       // the result block of the fetches above a run (afx_block.h: ResultBlock), one at a time: they are synchronous
   void* h_high = nullptr;         // ... and the page-locked host block it lands in (with the call's small inputs on their way up)
   size_t h_high_cap = 0;
   std::vector<Buf*> all_bufs();   // every Buf member above, each exactly once: ws_free and bytes() walk this list

@@ -2,9 +2,8 @@
 // reference's class signature (a TBaggingClassificationModel of TGbdtClassificationModel, Models/Bagging.h, Models/GBDT.cpp)
 // read from LightGBM's text form into the flat arrays of gbdt/afx_gbdt.h and uploaded once, with the Normalizer's scale and
 // offset and the outlier limits (ClassificationTestDataItem.cpp:36-41).  Plain host code: nothing here evaluates a tree,
-// and nothing here launches (afx_batch_fetch_class_signature is in afx_classification.cpp beside the feature fetch whose
-// launch it shares).  The reader checks every index the kernel will follow, so a text that is not what it claims to be is
-// refused here and never walked on the device.
+// and nothing here launches (afx_batch_fetch_class_signature is in afx_class_decision.cpp).  The reader checks every index
+// the kernel will follow, so a text that is not what it claims to be is refused here and never walked on the device.
 
 #include <charconv>
 #include <cmath>

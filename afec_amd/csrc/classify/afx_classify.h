@@ -1,6 +1,6 @@
 // afec_amd/csrc/classify/afx_classify.h -- the classification features' kernel (afx_classify.hip) and its launcher, shared
-// with the entry points of afx_classification.cpp.  Kept apart from afx_internal.h for the reason highlevel/afx_highlevel.h
-// gives: that header's launchers are the set a device mock has to implement, and this one is not part of it.
+// with the entry points of afx_classification.cpp and afx_class_decision.cpp.  Kept apart from afx_internal.h for the reason
+// highlevel/afx_highlevel.h gives; a device mock implements this launcher too.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // afec_amd/csrc/decide/afx_decide.h -- the class decision's kernel (afx_decide.hip) and its launcher, shared with the entry
-// points of afx_classification.cpp.  Kept apart from afx_internal.h for the reason gbdt/afx_gbdt.h gives: that header's launchers
-// are the set a device mock has to implement, and this one is not part of it.
+// points of afx_class_decision.cpp.  Kept apart from afx_internal.h for the reason highlevel/afx_highlevel.h gives; a device
+// mock implements this launcher too.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,7 +1,6 @@
 // afec_amd/csrc/gbdt/afx_gbdt.h -- the class signature's kernel (afx_gbdt.hip) and its launcher, shared with the entry
-// points of afx_model.cpp (which fills GbdtModel) and afx_classification.cpp (which launches).  Kept apart from
-// afx_internal.h for the reason highlevel/afx_highlevel.h gives: that header's launchers are the set a device mock has to
-// implement, and this one is not part of it.
+// points of afx_model.cpp (which fills GbdtModel) and afx_class_decision.cpp (which launches).  Kept apart from
+// afx_internal.h for the reason highlevel/afx_highlevel.h gives; a device mock implements this launcher too.
 #pragma once
 
 #include <hip/hip_runtime.h>

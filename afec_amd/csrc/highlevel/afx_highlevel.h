@@ -1,6 +1,7 @@
 // afec_amd/csrc/highlevel/afx_highlevel.h -- the high-level descriptors' kernel (afx_highlevel.hip) and its launcher, shared
-// with the entry point afx_batch_fetch_high_level (afx_high_level.cpp).  Kept apart from afx_internal.h: that header's
-// launchers are the set a device mock has to implement, and this one is not part of it yet.
+// with the entry point afx_batch_fetch_high_level (afx_high_level.cpp).  Kept apart from afx_internal.h, which the run's
+// translation units include and this fetch's need not reach; a device mock implements that header's launchers and the
+// four of the fetches above a run (this one, classify/, gbdt/, decide/), as tests/sanitize/mock_kernels.cpp does.
 #pragma once
 
 #include <hip/hip_runtime.h>

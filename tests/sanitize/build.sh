@@ -16,7 +16,7 @@ case $KIND in
 esac
 OUT=${AFX_SAN_DIR:-/tmp/afx_san}
 mkdir -p "$OUT"
-ABI="afec_amd/csrc/afx_plan.cpp afec_amd/csrc/afx_workspace.cpp afec_amd/csrc/afx_batch_plan.cpp afec_amd/csrc/afx_batch_create.cpp afec_amd/csrc/afx_batch_run.cpp afec_amd/csrc/afx_batch_fetch.cpp"
+ABI="afec_amd/csrc/afx_plan.cpp afec_amd/csrc/afx_workspace.cpp afec_amd/csrc/afx_batch_plan.cpp afec_amd/csrc/afx_batch_create.cpp afec_amd/csrc/afx_batch_run.cpp afec_amd/csrc/afx_batch_fetch.cpp afec_amd/csrc/afx_high_level.cpp afec_amd/csrc/afx_classification.cpp afec_amd/csrc/afx_class_decision.cpp afec_amd/csrc/afx_model.cpp"
 MOCK="tests/sanitize/mock_kernels.cpp tests/sanitize/hipstub/hip_stub.cpp"
 HOST="afec_amd/host/Crawler.cpp afec_amd/host/SampleAnalyser.cpp afec_amd/host/DescriptorColumns.cpp afec_amd/host/SqlitePool.cpp afec_amd/host/WaveFile.cpp afec_amd/host/SyntheticInput.cpp"
 FLAGS="-std=c++17 -O1 -g -fno-omit-frame-pointer $SAN -Itests/sanitize/hipstub -Iinclude -DAFX_SRC_HASH=\"mock\""

@@ -10,6 +10,10 @@
 #include <cstddef>
 #include <cstdint>
 
+// function qualifiers of headers that device and host code share (classify/afx_classify.h, decide/afx_decide.h)
+#define __host__
+#define __device__
+
 typedef enum hipError_t {
   hipSuccess = 0,
   hipErrorInvalidValue = 1,

@@ -1,4 +1,5 @@
-// tests/sanitize/mock_kernels.cpp -- TEST INFRASTRUCTURE ONLY: the launchers of afx_internal.h for the mock device of
+// tests/sanitize/mock_kernels.cpp -- TEST INFRASTRUCTURE ONLY: the launchers of afx_internal.h and of the four fetches above
+// a run (highlevel/afx_highlevel.h, classify/afx_classify.h, gbdt/afx_gbdt.h, decide/afx_decide.h) for the mock device of
 // tests/sanitize/hipstub.  No descriptor is computed here.  Each "kernel" walks exactly the tables its HIP counterpart
 // walks, touches every byte it would read or write ("device memory" is the host heap, so AddressSanitizer sees an
 // allocation the planner sized too small or an offset that points past an arena), asserts the invariants the real
@@ -16,7 +17,12 @@
 //   * statistics regimes: small_rows / need_long describe the frame offsets that were uploaded;
 //   * rhythm tracker: file rows are prefix sums, every 512/128 frame lies inside the arena, long-file tables are
 //     consistent with the files' long_slot;
-//   * LoadSample / resample tables: every file's source and destination ranges lie inside their arenas (touched).
+//   * LoadSample / resample tables: every file's source and destination ranges lie inside their arenas (touched);
+//   * the fetches above a run (afx_block.h lays their blocks out): frame_offset starts at 0 and never steps back, every
+//     record column the kernel reads is selected, every pointer is aligned for its type, no output overlaps an input or
+//     another output.  Their results are closed forms of (file, index), another one for every array, and of a few inputs
+//     (the levels, the features' last values, the signatures, the peaks and the strided scalars), so that the driver sees
+//     an array handed out from the wrong offset or an input that was not where the arguments point.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -27,6 +33,10 @@
 #include <vector>
 
 #include "../../afec_amd/csrc/afx_internal.h"
+#include "../../afec_amd/csrc/classify/afx_classify.h"
+#include "../../afec_amd/csrc/decide/afx_decide.h"
+#include "../../afec_amd/csrc/gbdt/afx_gbdt.h"
+#include "../../afec_amd/csrc/highlevel/afx_highlevel.h"
 #include "../../include/afx.h"
 
 namespace afx {
@@ -213,12 +223,13 @@ hipError_t launch_bands(const BandArgs& a, hipStream_t) {
 namespace {
 // the chunk walk of the time-domain kernels: `remaining` = samples of the buffer from the chunk's first frame on
 void time_body(const TimeArgs& a, bool acorr, void (*emit)(const TimeArgs&, int64_t, double)) {
-  MOCK_CHECK(a.pcm && a.chunks && a.remaining && a.rec);
+  // only the autocorrelation reads `remaining`: a half-wave batch that leaves nothing but the amplitude to hop_kernel has none
+  MOCK_CHECK(a.pcm && a.chunks && a.rec && (a.remaining || !acorr));
   check_tiling(a.chunks, a.n_chunks);
   for (int c = 0; c < a.n_chunks; ++c) {
     const Chunk& ch = a.chunks[c];
-    const int64_t rem = a.remaining[c];
     const int64_t need = (int64_t)(ch.nframes - 1) * kHop + kFft;
+    const int64_t rem = a.remaining ? a.remaining[c] : need;
     MOCK_CHECK(rem >= need, rem, need);
     const bool more_frames_follow = rem < (1 << 30) && rem - (int64_t)ch.nframes * kHop >= kFft;
     if (acorr) MOCK_CHECK(!more_frames_follow || (ch.nframes % 2) == 0, c, ch.nframes);   // a frame's partner does not depend on the cut
@@ -498,6 +509,223 @@ hipError_t launch_resample(unsigned char* raw, const ResampleFile* files, int n_
     longest = std::max(longest, f.n_in);
   }
   MOCK_CHECK(blocks == n_blocks && longest == max_n_in, blocks, n_blocks);
+  return hipSuccess;
+}
+
+// ---- the fetches above a run ----
+namespace {
+
+struct Span {
+  const void* p;
+  size_t bytes;
+  size_t align;
+};
+template <typename T>
+Span span(const T* p, size_t count) { return Span{p, count * sizeof(T), alignof(T)}; }
+
+// every array aligned for its type; no output overlaps another array
+void check_arrays(const std::vector<Span>& outputs, const std::vector<Span>& inputs) {
+  std::vector<Span> all(outputs);
+  all.insert(all.end(), inputs.begin(), inputs.end());
+  for (size_t i = 0; i < all.size(); ++i) {
+    MOCK_CHECK(all[i].bytes == 0 || all[i].p != nullptr, (long long)i);
+    MOCK_CHECK(((uintptr_t)all[i].p % all[i].align) == 0, (long long)i, (long long)all[i].align);
+  }
+  for (size_t i = 0; i < outputs.size(); ++i)
+    for (size_t j = 0; j < all.size(); ++j) {
+      if (i == j || !outputs[i].bytes || !all[j].bytes) continue;
+      const char *a0 = (const char*)outputs[i].p, *b0 = (const char*)all[j].p;
+      MOCK_CHECK(a0 + outputs[i].bytes <= b0 || b0 + all[j].bytes <= a0, (long long)i, (long long)j);
+    }
+}
+
+// the frames of every file; returns their total
+int64_t check_frame_offset(const int64_t* frame_offset, int n) {
+  MOCK_CHECK(frame_offset != nullptr && frame_offset[0] == 0, frame_offset ? frame_offset[0] : -1);
+  for (int i = 0; i < n; ++i) MOCK_CHECK(frame_offset[i + 1] >= frame_offset[i], i, frame_offset[i + 1]);
+  return frame_offset[n];
+}
+
+inline double read(const double* p) { return *(const volatile double*)p; }
+
+}  // namespace
+
+hipError_t launch_high_level(const HighArgs& a, hipStream_t) {
+  if (a.n_bufs <= 0) return hipSuccess;
+  const size_t n = (size_t)a.n_bufs;
+  const int64_t total = check_frame_offset(a.frame_offset, a.n_bufs);
+  const RecordLayout& l = a.lay;
+  const int32_t columns[] = {l.silence, l.f0_conf, l.rolloff, l.centroid, l.flatness, l.autocorr, l.flux, l.contrast, l.complexity, l.inharm, l.amp_peak, l.f0};
+  for (int32_t c : columns) MOCK_CHECK(c >= 0 && c < l.stride, c, l.stride);
+  MOCK_CHECK(l.bands >= 0 && l.bands + 28 <= l.stride, l.bands, l.stride);
+  MOCK_CHECK(total == 0 || a.rec != nullptr);
+  MOCK_CHECK(a.rt_scalars != nullptr && a.sample_rate > 0);
+  check_arrays({span(a.scalars, n * kHighScalars), span(a.signature, n * kHighSignatureFrames * kHighSignatureBands), span(a.pitch, (size_t)total),
+                span(a.peak, (size_t)total)},
+               {span(a.levels, a.levels ? n * 2 : 0), span(a.rec, (size_t)total * l.stride), span(a.frame_offset, n + 1), span(a.rt_scalars, n * 14)});
+  for (int file = 0; file < a.n_bufs; ++file) {
+    const int64_t row0 = a.frame_offset[file], frames = a.frame_offset[file + 1] - row0;
+    double* scalars = a.scalars + (size_t)file * kHighScalars;
+    double* signature = a.signature + (size_t)file * kHighSignatureFrames * kHighSignatureBands;
+    if (frames <= 0) {
+      for (int s = 0; s < kHighScalars; ++s) scalars[s] = 0.0;
+      for (int j = 0; j < kHighSignatureFrames * kHighSignatureBands; ++j) signature[j] = 0.0;
+      continue;
+    }
+    for (int64_t p = 0; p < frames; ++p) {
+      const double* r = a.rec + (row0 + p) * l.stride;
+      for (int32_t c : columns) (void)read(r + c);
+      for (int k = 0; k < 28; ++k) (void)read(r + l.bands + k);
+      a.pitch[row0 + p] = 3e3 * file + (double)p + 0.125;
+      a.peak[row0 + p] = 4e3 * file + (double)p + 0.0625;
+    }
+    for (int k = 0; k < 14; ++k) (void)read(a.rt_scalars + (size_t)file * 14 + k);
+    const double nan = std::nan("");
+    scalars[0] = a.levels ? (double)a.levels[2 * file] : nan;
+    scalars[1] = a.levels ? (double)a.levels[2 * file + 1] : nan;
+    for (int s = 2; s < kHighScalars; ++s) scalars[s] = 1e3 * file + s + 0.25;
+    for (int j = 0; j < kHighSignatureFrames * kHighSignatureBands; ++j) signature[j] = 2e3 * file + j + 0.5;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_classification_features(const ClassifyArgs& a, hipStream_t) {
+  if (a.n_bufs <= 0) return hipSuccess;
+  const size_t n = (size_t)a.n_bufs;
+  const int64_t total = check_frame_offset(a.frame_offset, a.n_bufs);
+  const RecordLayout& l = a.lay;
+  const int32_t scalar_columns[] = {l.srms, l.flatness, l.flux, l.contrast, l.complexity, l.f0_conf, l.amp_rms, l.silence};
+  for (int32_t c : scalar_columns) MOCK_CHECK(c >= 0 && c < l.stride, c, l.stride);
+  const int32_t band_columns[] = {l.sub_rms, l.sub_flat, l.sub_flux, l.sub_cplx, l.sub_contrast, l.mfcc};
+  for (int32_t c : band_columns) MOCK_CHECK(c >= 0 && c + kNumSub <= l.stride, c, l.stride);
+  MOCK_CHECK(l.bands >= 0 && l.bands + 28 <= l.stride, l.bands, l.stride);
+  MOCK_CHECK(total == 0 || a.rec != nullptr);
+  MOCK_CHECK(a.stats && a.rt_scalars && a.efflen12 && a.status);
+  check_arrays({span(a.features, n * kClassifyFeatures), span(a.non_finite, n)},
+               {span(a.efflen12, n), span(a.status, n), span(a.rec, (size_t)total * l.stride), span(a.frame_offset, n + 1),
+                span(a.stats, n * l.stride * 13), span(a.rt_scalars, n * 14)});
+  for (int file = 0; file < a.n_bufs; ++file) {
+    const int64_t row0 = a.frame_offset[file], frames = a.frame_offset[file + 1] - row0;
+    double* out = a.features + (size_t)file * kClassifyFeatures;
+    const int32_t status = *(const volatile int32_t*)(a.status + file);
+    (void)read(a.efflen12 + file);
+    if (frames <= 0 || status != 0) {
+      for (int j = 0; j < kClassifyFeatures; ++j) out[j] = 0.0;
+      a.non_finite[file] = 0;
+      continue;
+    }
+    for (int t = 0; t < kClassifyTimeFrames; ++t) {   // rows 0..43 and 64, 128, 256, 512 where the file has them
+      const int64_t frame = classify_time_frame(t);
+      if (frame >= frames) continue;
+      const double* r = a.rec + (row0 + frame) * l.stride;
+      for (int k = 0; k < 28; ++k) (void)read(r + l.bands + k);
+      for (int32_t c : scalar_columns) (void)read(r + c);
+    }
+    for (int k = 0; k < l.stride * 13; ++k) (void)read(a.stats + (size_t)file * l.stride * 13 + k);
+    for (int k = 0; k < 14; ++k) (void)read(a.rt_scalars + (size_t)file * 14 + k);
+    for (int j = 0; j < kClassifyFeatures; ++j) out[j] = 5e3 * file + j + 0.375;
+    a.non_finite[file] = 7 * file + 1;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_class_signature(const GbdtArgs& a, hipStream_t) {
+  if (a.n_bufs <= 0) return hipSuccess;
+  const size_t n = (size_t)a.n_bufs;
+  const GbdtModel& m = a.model;
+  check_frame_offset(a.frame_offset, a.n_bufs);
+  MOCK_CHECK(m.n_classes >= 2 && m.n_classes <= kGbdtMaxClasses && m.n_models >= 1 && m.n_models <= kGbdtMaxModels, m.n_classes, m.n_models);
+  MOCK_CHECK(m.early_stop_freq >= 1 && a.features && a.status);
+  // every model array, whole
+  MOCK_CHECK(m.tree_first && m.tree_first[0] == 0);
+  const int trees = m.tree_first[m.n_models];
+  size_t nodes = 0, leaves = 0;
+  for (int mi = 0; mi < m.n_models; ++mi) {
+    MOCK_CHECK(m.tree_first[mi + 1] > m.tree_first[mi] && (m.tree_first[mi + 1] - m.tree_first[mi]) % m.n_classes == 0, mi);
+    MOCK_CHECK(m.objective[mi] == kGbdtSoftmax || m.objective[mi] == kGbdtOneVsAll, mi);
+    (void)read(m.sigmoid + mi);
+  }
+  for (int t = 0; t < trees; ++t) {
+    MOCK_CHECK(m.num_leaves[t] >= 1 && (size_t)m.node_first[t] == nodes && (size_t)m.leaf_first[t] == leaves, t);
+    nodes += (size_t)m.num_leaves[t] - 1;
+    leaves += (size_t)m.num_leaves[t];
+  }
+  for (size_t g = 0; g < nodes; ++g) {
+    MOCK_CHECK(m.split_feature[g] >= 0 && m.split_feature[g] < kGbdtFeatures && !(m.decision_type[g] & 1), (long long)g);
+    (void)*(const volatile int32_t*)(m.left_child + g);
+    (void)*(const volatile int32_t*)(m.right_child + g);
+    (void)read(m.threshold + g);
+  }
+  for (size_t j = 0; j < leaves; ++j) (void)read(m.leaf_value + j);
+  for (int j = 0; j < kGbdtFeatures; ++j) {
+    (void)read(m.scale + j);
+    (void)read(m.offset + j);
+    MOCK_CHECK(read(m.limits + j) > 0.0, j);
+  }
+  check_arrays({span(a.signature, n * m.n_classes), span(a.iterations_used, n * m.n_models), span(a.non_finite, n)},
+               {span(a.features, n * kGbdtFeatures), span(a.frame_offset, n + 1), span(a.status, n), span(m.tree_first, (size_t)m.n_models + 1),
+                span(m.objective, (size_t)m.n_models), span(m.sigmoid, (size_t)m.n_models), span(m.num_leaves, (size_t)trees), span(m.node_first, (size_t)trees),
+                span(m.leaf_first, (size_t)trees), span(m.split_feature, nodes), span(m.decision_type, nodes), span(m.left_child, nodes),
+                span(m.right_child, nodes), span(m.threshold, nodes), span(m.leaf_value, leaves), span(m.scale, (size_t)kGbdtFeatures),
+                span(m.offset, (size_t)kGbdtFeatures), span(m.limits, (size_t)kGbdtFeatures)});
+  for (int file = 0; file < a.n_bufs; ++file) {
+    const bool empty = a.frame_offset[file + 1] - a.frame_offset[file] <= 0 || a.status[file] != 0;
+    const double* f = a.features + (size_t)file * kGbdtFeatures;
+    int bad = 0;
+    if (!empty)
+      for (int j = 0; j < kGbdtFeatures; ++j) bad += std::isfinite(read(f + j)) ? 0 : 1;
+    for (int c = 0; c < m.n_classes; ++c) a.signature[(size_t)file * m.n_classes + c] = (empty || bad) ? 0.0f : (float)(f[kGbdtFeatures - 1 - c] + 0.5 * (c + 1));
+    for (int mi = 0; mi < m.n_models; ++mi) a.iterations_used[(size_t)file * m.n_models + mi] = (empty || bad) ? 0 : 100 * file + mi + 1;
+    a.non_finite[file] = bad;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_class_decision(const DecideArgs& a, hipStream_t) {
+  if (a.n_files <= 0) return hipSuccess;
+  const size_t n = (size_t)a.n_files;
+  const int64_t total = check_frame_offset(a.frame_offset, a.n_files);
+  const int k = a.category_signature ? a.n_categories : 0;
+  MOCK_CHECK(a.class_signature || a.category_signature);
+  MOCK_CHECK(!a.category_signature || (a.n_categories >= 2 && a.n_categories <= kDecideMaxCategories), a.n_categories);
+  MOCK_CHECK((a.loop_class == 0 && a.oneshot_class == 1) || (a.loop_class == 1 && a.oneshot_class == 0), a.loop_class, a.oneshot_class);
+  MOCK_CHECK(a.none_category >= -1 && a.none_category < std::max(k, 0), a.none_category, k);
+  MOCK_CHECK(a.peak_stride >= 1 && (total == 0 || a.peak != nullptr), a.peak_stride);
+  MOCK_CHECK(a.silence_floor > 0.0630 && a.silence_floor < 0.0631);
+  const DecideScalar scalars[] = {a.efflen24, a.onset_count, a.percussive_confidence, a.complex_confidence, a.flux_mean};
+  std::vector<Span> inputs = {span(a.class_signature, a.class_signature ? n * 2 : 0), span(a.category_signature, n * (size_t)k),
+                              span(a.frame_offset, n + 1), span(a.status, a.status ? n : 0), span(a.non_finite_in, a.non_finite_in ? n : 0),
+                              span(a.peak, total ? (size_t)(total - 1) * (size_t)a.peak_stride + 1 : 0)};
+  for (const DecideScalar& s : scalars) {
+    MOCK_CHECK(s.p != nullptr && s.stride >= 1, s.stride);
+    inputs.push_back(span(s.p, (n - 1) * (size_t)s.stride + 1));
+  }
+  check_arrays({span(a.class_strengths, n * 2), span(a.classes, n * 2), span(a.category_strengths, n * (size_t)k), span(a.categories, n * (size_t)k),
+                span(a.confidences, n * 2), span(a.flags, n), span(a.non_finite, n)},
+               inputs);
+  for (int file = 0; file < a.n_files; ++file) {
+    const int64_t row0 = a.frame_offset[file], frames = a.frame_offset[file + 1] - row0;
+    const int bad = a.non_finite_in ? a.non_finite_in[file] : 0;
+    const bool refused = a.status && a.status[file] != 0;
+    a.non_finite[file] = bad;
+    double sum = 0.0;
+    for (const DecideScalar& s : scalars) sum += read(&s.p[(int64_t)file * s.stride]);
+    double peaks = 0.0;
+    for (int64_t f = 0; f < frames; ++f) peaks += read(a.peak + (row0 + f) * a.peak_stride);
+    const bool zeros = frames <= 0 || refused || bad != 0;
+    for (int c = 0; c < kDecideClasses; ++c) {
+      const bool there = !zeros && a.class_signature;
+      a.class_strengths[(size_t)file * 2 + c] = there ? (double)a.class_signature[(size_t)file * 2 + c] + 0.25 : 0.0;
+      a.classes[(size_t)file * 2 + c] = there ? 10 * file + c : -1;
+    }
+    for (int j = 0; j < k; ++j) {
+      a.category_strengths[(size_t)file * k + j] = zeros ? 0.0 : (double)a.category_signature[(size_t)file * k + j] + 0.75;
+      a.categories[(size_t)file * k + j] = zeros ? -1 : 1000 + 100 * file + j;
+    }
+    a.confidences[(size_t)file * 2] = zeros ? -1.0 : sum;
+    a.confidences[(size_t)file * 2 + 1] = zeros ? -1.0 : peaks;
+    a.flags[file] = zeros ? 0 : 64 * file + 32 + 16 * (a.none_category >= 0 ? 1 : 0) + 2 * a.use_heuristics + a.loop_class;
+  }
   return hipSuccess;
 }
 

@@ -3,8 +3,9 @@
 # profiles/<round>/tsan_crawler.txt.
 #   1. ASan + UBSan: the WAV reader, the column encoder and the oracle (tests/sanitize/sanitize_main.cpp);
 #   2. ASan + UBSan: the C-ABI's host code (afec_amd/csrc/afx_plan / workspace / batch_plan / batch_create / batch_run /
-#      batch_fetch .cpp) on the mock device of tests/sanitize/hipstub + mock_kernels.cpp, fuzzed ragged batches
-#      (tests/sanitize/fuzz_host_abi.cpp), and the crawler driver on the same stack;
+#      batch_fetch / high_level / classification / class_decision / model .cpp) on the mock device of tests/sanitize/hipstub +
+#      mock_kernels.cpp, fuzzed ragged batches and the fetches above a run (tests/sanitize/fuzz_host_abi.cpp), and the
+#      crawler driver on the same stack;
 #   3. TSan: the streaming sharded crawler + sqlite pool above that stack (tests/sanitize/tsan_crawler.cpp: G = 1, 2, 8
 #      mock devices, injected batch failures, a lost device, an external abort), and the C-ABI fuzz with four threads on
 #      shared plans.
@@ -22,7 +23,7 @@ tests/sanitize/build.sh tsan > /dev/null
   echo "# 1. g++ -fsanitize=address,undefined (-fno-sanitize-recover): tests/sanitize/sanitize_main.cpp + afec_amd/host/{WaveFile,DescriptorColumns}.cpp + oracle/*.c"
   ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 /tmp/afx_san/sanitize 2>&1
   echo "exit code $?"
-  echo "# 2. the same flags: afec_amd/csrc/afx_{plan,workspace,batch_plan,batch_create,batch_run,batch_fetch}.cpp on the mock device"
+  echo "# 2. the same flags: afec_amd/csrc/afx_{plan,workspace,batch_plan,batch_create,batch_run,batch_fetch,high_level,classification,class_decision,model}.cpp on the mock device"
   echo "#    (tests/sanitize/hipstub, mock_kernels.cpp), tests/sanitize/fuzz_host_abi.cpp <rounds> <seed> <threads>"
   for SEED in 1 2 3; do
     ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1 /tmp/afx_san/fuzz_host_abi_asan 250 $SEED 1 2>&1 | tail -25
