@@ -69,6 +69,8 @@ CF_TIME_FRAMES, NUM_CLASSIFICATION_FEATURES, NUM_CF_SILENCE = 48, 1680, 21
 # afx_batch_fetch_class_decision: the mask's bits, afx_decision_out.flags, the scalars afx_decide reads per file
 D_CLASS_DECISION_INPUTS = D_CLASSIFICATION_INPUTS | D_AMPLITUDE_PEAK
 DECISION_IS_ONESHOT, DECISION_IS_LOOP, DECISION_OVERRIDDEN = 1, 2, 4
+# afx_batch_fetch_high_level_text: the columns that come back as text (AFX_HLT_*)
+HLT_COLUMNS = ["spectrum_signature", "pitch", "peak"]
 DECISION_SCALARS = ["effectve_length_24dB", "rhythm_percussive_onset_count", "rhythm_percussive_tempo_confidence",
                     "rhythm_complex_tempo_confidence", "spectral_flux_mean"]
 PRECISION_F64, PRECISION_F32 = 0, 1
@@ -90,6 +92,7 @@ EXPORTS = [
     "afx_batch_fetch_classification_features", "afx_classification_feature_name", "afx_plan_get_silence_features",
     "afx_model_create_from_lightgbm", "afx_model_destroy", "afx_model_get_info", "afx_batch_fetch_class_signature",
     "afx_model_evaluate_features", "afx_batch_fetch_class_decision", "afx_decide",
+    "afx_batch_high_level_text_capacity", "afx_batch_fetch_high_level_text", "afx_format_json_g9",
 ]
 RAW_I16, RAW_I24, RAW_F32, RAW_I32, RAW_F64 = 0, 1, 2, 3, 4
 
@@ -163,6 +166,11 @@ class _LoadInfo(ctypes.Structure):
 
 class _HighOut(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("scalars", "signature", "pitch", "peak", "status")]
+
+
+class _HighTextOut(ctypes.Structure):
+    _fields_ = [("scalars", ctypes.c_void_p), ("text", ctypes.c_void_p), ("text_capacity", ctypes.c_int64), ("begin", ctypes.c_void_p),
+                ("length", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
 class _DecisionDesc(ctypes.Structure):
@@ -282,6 +290,10 @@ def load_library():
     L.afx_model_evaluate_features.argtypes = [vp, vp, i32, vp, vp, vp]
     L.afx_batch_fetch_class_decision.argtypes = [vp, ctypes.POINTER(_DecisionDesc), ctypes.POINTER(_DecisionOut)]
     L.afx_decide.argtypes = [vp, ctypes.POINTER(_DecisionIn), ctypes.POINTER(_DecisionOut)]
+    L.afx_batch_high_level_text_capacity.restype = i64
+    L.afx_batch_high_level_text_capacity.argtypes = [vp]
+    L.afx_batch_fetch_high_level_text.argtypes = [vp, ctypes.POINTER(_LoadInfo), ctypes.POINTER(_HighTextOut)]
+    L.afx_format_json_g9.argtypes = [vp, vp, i64, vp, vp, i32, vp, i64, vp, vp]
     _lib = L
     return L
 
@@ -345,6 +357,42 @@ def decide(plan, peaks, frame_offset, scalars, class_signature=None, category_si
     out, res = _decision_out(n, class_signature is not None, k)
     _check(plan.L, plan.L.afx_decide(plan.h, ctypes.byref(d), ctypes.byref(out)))
     return res
+
+
+def json_g9_capacity(count, inner=0):
+    """the bytes afx_format_json_g9 wants for a column of `count` values: 2 + 17 values + 2 rows"""
+    return 2 + 17 * count + (2 * (count // inner) if inner else 0)
+
+
+def format_json_g9(plan, columns):
+    """afx_format_json_g9: the text kernel of Batch.fetch_high_level_text on doubles of the caller's, no batch.  columns: a
+    list of 1-D arrays (written as "[a,b,c]") and 2-D arrays ([rows][W], written as "[[a,b],[c,d]]") -> list of bytes, every
+    number as snprintf("%.9g") writes it (NaN, INF, -INF for the values that are no numbers)"""
+    arrays = [np.ascontiguousarray(c, dtype=np.float64) for c in columns]
+    if any(a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[1] == 0) for a in arrays):
+        raise ValueError("a column is a 1-D array or a 2-D array of rows that are not empty")
+    inner = np.array([a.shape[1] if a.ndim == 2 else 0 for a in arrays] + [0], dtype=np.int32)
+    offset = np.concatenate([[0], np.cumsum([a.size for a in arrays])]).astype(np.int64)
+    return format_json_g9_raw(plan, np.concatenate([a.reshape(-1) for a in arrays] + [np.zeros(0)]), offset, inner[:len(arrays)])["texts"]
+
+
+def format_json_g9_raw(plan, values, column_offset, inner, text_capacity=None):
+    """afx_format_json_g9 with the arrays as the C call takes them (the checks are the library's) -> dict: "texts" (list of
+    bytes), "begin" int64 [n], "length" int32 [n], "capacity" (the bytes of text asked for)"""
+    values = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    column_offset = np.ascontiguousarray(column_offset, dtype=np.int64).reshape(-1)
+    inner = np.ascontiguousarray(inner, dtype=np.int32).reshape(-1)
+    n = inner.size
+    if column_offset.size != n + 1:
+        raise ValueError("column_offset holds one offset more than there are columns")
+    if text_capacity is None:
+        text_capacity = sum(json_g9_capacity(max(0, int(column_offset[c + 1] - column_offset[c])), max(0, int(inner[c]))) for c in range(n))
+    text = np.zeros(max(1, text_capacity), dtype=np.uint8)
+    begin, length = np.zeros(max(1, n), dtype=np.int64), np.zeros(max(1, n), dtype=np.int32)
+    _check(plan.L, plan.L.afx_format_json_g9(plan.h, values.ctypes.data, values.size, column_offset.ctypes.data, inner.ctypes.data, n,
+                                             text.ctypes.data, text_capacity, begin.ctypes.data, length.ctypes.data))
+    return {"texts": [text[begin[c]:begin[c] + length[c]].tobytes() for c in range(n)], "begin": begin[:n], "length": length[:n],
+            "capacity": text_capacity}
 
 
 def pinned_array(shape, dtype):
@@ -667,6 +715,36 @@ class Batch:
             for i, d in enumerate(levels):
                 info[i].peak_value, info[i].rms_value = d["peak_value"], d["rms_value"]
         _check(self.L, self.L.afx_batch_fetch_high_level(self.h, info, ctypes.byref(out)))
+        return res
+
+    def high_level_text_capacity(self):
+        """afx_batch_high_level_text_capacity: the bytes of text fetch_high_level_text may need for this batch"""
+        return int(self.L.afx_batch_high_level_text_capacity(self.h))
+
+    def fetch_high_level_text(self, levels=None, text=None):
+        """afx_batch_fetch_high_level_text: the scalars of fetch_high_level and, in place of its three arrays, their text as
+        the reference's database stores it (JSON, every number as "%.9g").  dict: "scalars" [n_bufs][15], "status" [n_bufs],
+        "text" uint8 [capacity], "begin" int64 [n_bufs][3], "length" int32 [n_bufs][3] (HLT_COLUMNS order), and per column
+        name a list of n_bufs bytes objects.  text: a uint8 array to fill (page-locked memory, say) in place of a new one."""
+        n = self.n_bufs
+        capacity = self.high_level_text_capacity()
+        if text is None:
+            text = np.zeros(max(1, capacity), dtype=np.uint8)
+        res = {"scalars": np.zeros((n, NUM_HL_SCALARS)), "status": np.zeros(n, dtype=np.int32), "text": text,
+               "begin": np.zeros((n, len(HLT_COLUMNS)), dtype=np.int64), "length": np.zeros((n, len(HLT_COLUMNS)), dtype=np.int32)}
+        out = _HighTextOut(text_capacity=text.size)
+        for k in ("scalars", "status", "text", "begin", "length"):
+            setattr(out, k, res[k].ctypes.data if res[k].size else None)
+        info = None
+        if levels is not None:
+            if len(levels) != n:
+                raise ValueError("levels must hold one load info per buffer")
+            info = (_LoadInfo * max(1, n))()
+            for i, d in enumerate(levels):
+                info[i].peak_value, info[i].rms_value = d["peak_value"], d["rms_value"]
+        _check(self.L, self.L.afx_batch_fetch_high_level_text(self.h, info, ctypes.byref(out)))
+        for c, name in enumerate(HLT_COLUMNS):
+            res[name] = [text[res["begin"][i, c]:res["begin"][i, c] + res["length"][i, c]].tobytes() for i in range(n)]
         return res
 
     def fetch_classification_features(self):

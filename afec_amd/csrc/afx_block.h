@@ -1,5 +1,6 @@
-// afec_amd/csrc/afx_block.h -- how the fetches above a run (afx_high_level.cpp, afx_classification.cpp,
-// afx_class_decision.cpp) lay out memory, host only.  A block holds typed arrays behind one another, the same way on the
+// afec_amd/csrc/afx_block.h -- how the fetches above a run (afx_high_level.cpp, afx_high_level_text.cpp,
+// afx_classification.cpp, afx_class_decision.cpp) lay out memory, host only.  A block holds typed arrays behind one
+// another, the same way on the
 // device and on the host, so that one transfer moves a run of them.  Layout hands out the offsets and is the only place a
 // byte offset is formed; each fetch names its block once as a struct of offsets with point() (the kernel's arguments into a
 // block at `base`) and hand_out() (the host copy into the caller's arrays).  ResultBlock is the batch's reused block behind
@@ -10,6 +11,7 @@
 
 #include "afx_host.h"
 #include "classify/afx_classify.h"
+#include "highlevel/afx_highlevel.h"
 
 namespace afx {
 namespace host {
@@ -94,6 +96,37 @@ class DeviceBlock {
  private:
   void* p_ = nullptr;
 };
+
+// The high-level block: what high_level_kernel writes and the fetch brings back (scalars, signature, pitch, peak), behind
+// it the caller's peak / rms pairs on their way up.
+struct HighBlock {
+  size_t n, frames, scalars, signature, pitch, peak, levels;
+  HighBlock(Layout& l, size_t n_bufs, size_t total_frames) : n(n_bufs), frames(total_frames) {
+    scalars = l.take<double>(n * kHighScalars);
+    signature = l.take<double>(n * kHighSignatureFrames * kHighSignatureBands);
+    pitch = l.take<double>(frames);
+    peak = l.take<double>(frames);
+    levels = l.take<float>(n * 2);
+  }
+  void point(HighArgs* a, char* base, bool with_levels) const {
+    a->scalars = at<double>(base, scalars);
+    a->signature = at<double>(base, signature);
+    a->pitch = at<double>(base, pitch);
+    a->peak = at<double>(base, peak);
+    a->levels = with_levels ? at<float>(base, levels) : nullptr;
+  }
+  void hand_out(const char* host, afx_high_out* out) const {
+    if (out->scalars) std::memcpy(out->scalars, host + scalars, n * kHighScalars * sizeof(double));
+    if (out->signature) std::memcpy(out->signature, host + signature, n * kHighSignatureFrames * kHighSignatureBands * sizeof(double));
+    if (out->pitch && frames) std::memcpy(out->pitch, host + pitch, frames * sizeof(double));
+    if (out->peak && frames) std::memcpy(out->peak, host + peak, frames * sizeof(double));
+  }
+};
+
+// afx_high_level.cpp: the launch the two high-level fetches share.  Reserves the batch's result block for `layout` (which
+// starts with `hb`) behind the checks of afx_batch_fetch_high_level, uploads the levels where there are any and launches
+// high_level_kernel, all on the batch's stream; nothing is downloaded.  rb->n == 0: an empty batch, nothing launched.
+int launch_high_level_block(afx_batch* b, const char* who, const afx_load_info* levels, const Layout& layout, const HighBlock& hb, ResultBlock* rb);
 
 // What classification_features_kernel writes and the feature fetch brings back (features, counts), then what goes up for it
 // in one transfer: effectve_length_12dB for the features, effectve_length_24dB for the class decision's heuristics, the

@@ -590,6 +590,44 @@ typedef struct {
 } afx_decision_in;
 int afx_decide(const afx_plan* plan, const afx_decision_in* in, afx_decision_out* out);
 
+/* ---- the high-level vector columns as text: SToJSON (SqliteSampleDescriptorPool.cpp:316-419) ---- *
+ * The reference's high-level `assets` table stores spectrum_signature_VVR, pitch_VR and peak_VR as TEXT: JSON lists, "," alone
+ * between the numbers, every number as ToString(double, "%.9g") writes it (Str.cpp:4027-4070): the bytes of
+ * snprintf("%.9g") in the C locale -- nine significant digits correctly rounded from the binary value, ties to even,
+ * trailing zeros stripped, exponent form below 1e-4 and from 1e9 on, "-0" for -0.0 -- and "NaN", "INF", "-INF" for the
+ * values that are no numbers.  1 000 to 2 600 numbers per file: formatted on the GPU (csrc/text/) from the arrays
+ * afx_batch_fetch_high_level would return, which stay in device memory; the text comes back in their place.  A buffer
+ * without frames has the all-zero signature's text and "[]" twice.
+ * Every column's text lies in a slot of `text` that depends only on the batch's frame counts (2 + 17 values + 2 rows
+ * bytes; the text starts at the slot's first byte, what is behind `length` is not written): begin[] is the same on every
+ * fetch of a batch, and a column is bound with sqlite3_bind_text(stmt, i, text + begin[..], length[..], SQLITE_STATIC). */
+enum { AFX_HLT_SPECTRUM_SIGNATURE = 0, AFX_HLT_PITCH, AFX_HLT_PEAK, AFX_NUM_HLT_COLUMNS };
+typedef struct {
+  double*  scalars;        /* [n_bufs][AFX_NUM_HL_SCALARS], as afx_high_out: REAL columns need no text */
+  char*    text;           /* [text_capacity], not NUL-terminated                                       */
+  int64_t  text_capacity;
+  int64_t* begin;          /* [n_bufs][AFX_NUM_HLT_COLUMNS] offsets into text                           */
+  int32_t* length;         /* [n_bufs][AFX_NUM_HLT_COLUMNS]                                             */
+  int32_t* status;         /* [n_bufs] or NULL: repeats buf_status                                      */
+} afx_high_text_out;       /* scalars and status may be NULL */
+/* the text_capacity that is enough for any content of this batch's buffers; -1 for NULL */
+int64_t afx_batch_high_level_text_capacity(const afx_batch* batch);
+/* As afx_batch_fetch_high_level (same checks, same kernel into the same block), the text kernel behind it on the batch's
+ * stream, one transfer of the scalars, the text and its index.  AFX_ERR_INVALID_ARG also for a text_capacity below
+ * afx_batch_high_level_text_capacity: nothing is written then.  Synchronous. */
+int afx_batch_fetch_high_level_text(afx_batch* batch, const afx_load_info* levels /* [n_bufs] or NULL */, afx_high_text_out* out);
+/* The same kernel on doubles the caller holds.  Column c is values[column_offset[c] .. column_offset[c + 1]); inner[c] = 0
+ * writes it as a flat list "[a,b,c]", inner[c] = W > 0 as rows of W, "[[a,b],[c,d]]" (W must divide the column's length);
+ * an empty column is "[]".  text_capacity must be at least the sum over the columns of 2 + 17 values + 2 rows.  Not the
+ * crawl's path: device memory of its own on the plan's device, the default stream.  Synchronous.  AFX_ERR_INVALID_ARG:
+ * offsets that do not start at 0, step back or do not end at n_values, an inner that is negative or does not divide its
+ * column, a column of more than 100 000 000 values, a capacity that is too small. */
+int afx_format_json_g9(const afx_plan* plan, const double* values, int64_t n_values,
+                       const int64_t* column_offset /* [n_columns + 1], starts at 0, never steps back */,
+                       const int32_t* inner /* [n_columns]; 0: VR, W: VVR, W must divide the column */,
+                       int32_t n_columns, char* text, int64_t text_capacity,
+                       int64_t* begin /* [n_columns] */, int32_t* length /* [n_columns] */);
+
 /* Page-locked host memory for PCM and result arrays: transfers from / to such buffers run at the
  * host link's rate (pageable memory is staged by the runtime at a fraction of it). */
 void* afx_host_alloc(int64_t bytes);
