@@ -71,6 +71,9 @@ D_CLASS_DECISION_INPUTS = D_CLASSIFICATION_INPUTS | D_AMPLITUDE_PEAK
 DECISION_IS_ONESHOT, DECISION_IS_LOOP, DECISION_OVERRIDDEN = 1, 2, 4
 # afx_batch_fetch_high_level_text: the columns that come back as text (AFX_HLT_*)
 HLT_COLUMNS = ["spectrum_signature", "pitch", "peak"]
+# afx_batch_fetch_high_level_row: the nine text columns of the reference's high-level table, in its order (AFX_HLR_*)
+HLR_COLUMNS = ["class_signature", "classes", "class_strengths", "category_signature", "categories", "category_strengths",
+               "spectrum_signature", "pitch", "peak"]
 DECISION_SCALARS = ["effectve_length_24dB", "rhythm_percussive_onset_count", "rhythm_percussive_tempo_confidence",
                     "rhythm_complex_tempo_confidence", "spectral_flux_mean"]
 PRECISION_F64, PRECISION_F32 = 0, 1
@@ -93,6 +96,7 @@ EXPORTS = [
     "afx_model_create_from_lightgbm", "afx_model_destroy", "afx_model_get_info", "afx_batch_fetch_class_signature",
     "afx_model_evaluate_features", "afx_batch_fetch_class_decision", "afx_decide",
     "afx_batch_high_level_text_capacity", "afx_batch_fetch_high_level_text", "afx_format_json_g9",
+    "afx_batch_high_level_row_capacity", "afx_batch_fetch_high_level_row", "afx_format_class_json",
 ]
 RAW_I16, RAW_I24, RAW_F32, RAW_I32, RAW_F64 = 0, 1, 2, 3, 4
 
@@ -191,6 +195,28 @@ class _DecisionIn(ctypes.Structure):
                 ("category_signature", ctypes.c_void_p), ("peaks", ctypes.c_void_p), ("frame_offset", ctypes.c_void_p),
                 ("scalars", ctypes.c_void_p), ("non_finite", ctypes.c_void_p), ("loop_class", ctypes.c_int32),
                 ("oneshot_class", ctypes.c_int32), ("use_heuristics", ctypes.c_int32), ("category_none_class", ctypes.c_int32)]
+
+
+class _Name(ctypes.Structure):
+    _fields_ = [("text", ctypes.c_char_p), ("length", ctypes.c_int32)]
+
+
+class _RowDesc(ctypes.Structure):
+    _fields_ = [("decision", _DecisionDesc), ("class_names", ctypes.POINTER(_Name)), ("n_class_names", ctypes.c_int32),
+                ("n_category_names", ctypes.c_int32), ("category_names", ctypes.POINTER(_Name))]
+
+
+class _RowOut(ctypes.Structure):
+    _fields_ = [("scalars", ctypes.c_void_p), ("text", ctypes.c_void_p), ("text_capacity", ctypes.c_int64), ("begin", ctypes.c_void_p),
+                ("length", ctypes.c_void_p), ("flags", ctypes.c_void_p), ("non_finite", ctypes.c_void_p), ("confidences", ctypes.c_void_p),
+                ("status", ctypes.c_void_p)]
+
+
+class _ClassJsonIn(ctypes.Structure):
+    _fields_ = [("n_files", ctypes.c_int32), ("n_categories", ctypes.c_int32), ("class_signature", ctypes.c_void_p),
+                ("class_strengths", ctypes.c_void_p), ("classes", ctypes.c_void_p), ("category_signature", ctypes.c_void_p),
+                ("category_strengths", ctypes.c_void_p), ("categories", ctypes.c_void_p), ("class_names", ctypes.POINTER(_Name)),
+                ("category_names", ctypes.POINTER(_Name))]
 
 
 class _StatsOut(ctypes.Structure):
@@ -294,6 +320,10 @@ def load_library():
     L.afx_batch_high_level_text_capacity.argtypes = [vp]
     L.afx_batch_fetch_high_level_text.argtypes = [vp, ctypes.POINTER(_LoadInfo), ctypes.POINTER(_HighTextOut)]
     L.afx_format_json_g9.argtypes = [vp, vp, i64, vp, vp, i32, vp, i64, vp, vp]
+    L.afx_batch_high_level_row_capacity.restype = i64
+    L.afx_batch_high_level_row_capacity.argtypes = [vp, ctypes.POINTER(_RowDesc)]
+    L.afx_batch_fetch_high_level_row.argtypes = [vp, ctypes.POINTER(_LoadInfo), ctypes.POINTER(_RowDesc), ctypes.POINTER(_RowOut)]
+    L.afx_format_class_json.argtypes = [vp, ctypes.POINTER(_ClassJsonIn), vp, i64, vp, vp]
     _lib = L
     return L
 
@@ -393,6 +423,70 @@ def format_json_g9_raw(plan, values, column_offset, inner, text_capacity=None):
                                              text.ctypes.data, text_capacity, begin.ctypes.data, length.ctypes.data))
     return {"texts": [text[begin[c]:begin[c] + length[c]].tobytes() for c in range(n)], "begin": begin[:n], "length": length[:n],
             "capacity": text_capacity}
+
+
+def _names(names):
+    """a list of str / bytes -> (ctypes array of afx_name or None, what keeps its bytes alive)"""
+    if not names:
+        return None, []
+    raw = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in names]
+    arr = (_Name * len(raw))()
+    for i, r in enumerate(raw):
+        arr[i].text, arr[i].length = r, len(r)
+    return arr, raw
+
+
+def names_slot_bytes(names):
+    """the bytes of a column of names that holds every one of them once: 2 + the sum of length + 3"""
+    return 2 + sum(len(s.encode("utf-8") if isinstance(s, str) else s) + 3 for s in names or [])
+
+
+def class_json_file_bytes(class_names, category_names):
+    """the bytes of one file's six class slots in afx_format_class_json's text: they lie one behind the other, file after file"""
+    return (2 * json_g9_capacity(len(class_names or [])) + names_slot_bytes(class_names)
+            + 2 * json_g9_capacity(len(category_names or [])) + names_slot_bytes(category_names))
+
+
+def format_class_json(plan, class_signature=None, class_strengths=None, classes=None, class_names=None, category_signature=None,
+                      category_strengths=None, categories=None, category_names=None, n_files=None, text=None):
+    """afx_format_class_json: the class columns' text kernel of Batch.fetch_high_level_row on arrays of the caller's, no batch.
+    The class arrays are [n][2] (float32 signature, float64 strengths, int32 picks, -1 padded), the category arrays [n][K];
+    either triple may be left out (its columns are "[]").  -> dict: "texts" [n][6] bytes (HLR_COLUMNS[:6] order), "text",
+    "begin" int64 [n][6], "length" int32 [n][6], "capacity".  text: a uint8 array to fill in place of a new one."""
+    d = _ClassJsonIn()
+    keep = []
+    n = n_files
+
+    def take(a, dtype, width):
+        nonlocal n
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.ndim != 2 or (width is not None and a.shape[1] != width) or (n is not None and a.shape[0] != n):
+            raise ValueError("the arrays hold one row per file, 2 wide for the classes and K for the categories")
+        n = a.shape[0]
+        keep.append(a)
+        return a.ctypes.data
+
+    d.class_signature, d.class_strengths, d.classes = take(class_signature, np.float32, 2), take(class_strengths, np.float64, 2), take(classes, np.int32, 2)
+    k = None
+    for name, a, dtype in (("category_signature", category_signature, np.float32), ("category_strengths", category_strengths, np.float64),
+                           ("categories", categories, np.int32)):
+        setattr(d, name, take(a, dtype, k))
+        if a is not None:
+            k = keep[-1].shape[1]
+    d.n_files, d.n_categories = n or 0, k or 0
+    d.class_names, raw0 = _names(class_names)
+    d.category_names, raw1 = _names(category_names)
+    capacity = (n or 0) * class_json_file_bytes(class_names if d.classes else None, category_names if d.categories else None)
+    if text is None:
+        text = np.zeros(max(1, capacity), dtype=np.uint8)
+    rows = max(1, n or 0)
+    begin, length = np.zeros((rows, 6), dtype=np.int64), np.zeros((rows, 6), dtype=np.int32)
+    _check(plan.L, plan.L.afx_format_class_json(plan.h, ctypes.byref(d), text.ctypes.data, text.size, begin.ctypes.data, length.ctypes.data))
+    n = n or 0
+    return {"texts": [[text[begin[i, c]:begin[i, c] + length[i, c]].tobytes() for c in range(6)] for i in range(n)], "text": text,
+            "begin": begin[:n], "length": length[:n], "capacity": capacity}
 
 
 def pinned_array(shape, dtype):
@@ -744,6 +838,52 @@ class Batch:
                 info[i].peak_value, info[i].rms_value = d["peak_value"], d["rms_value"]
         _check(self.L, self.L.afx_batch_fetch_high_level_text(self.h, info, ctypes.byref(out)))
         for c, name in enumerate(HLT_COLUMNS):
+            res[name] = [text[res["begin"][i, c]:res["begin"][i, c] + res["length"][i, c]].tobytes() for i in range(n)]
+        return res
+
+    def _row_desc(self, class_model, category_model, class_names, category_names, loop_class, oneshot_class, use_heuristics,
+                  category_none_class):
+        d = _RowDesc()
+        d.decision = _DecisionDesc(class_model=class_model.h if class_model else None, loop_class=loop_class, oneshot_class=oneshot_class,
+                                   use_heuristics=int(bool(use_heuristics)), category_model=category_model.h if category_model else None,
+                                   category_none_class=category_none_class)
+        d.class_names, raw0 = _names(class_names)
+        d.category_names, raw1 = _names(category_names)
+        d.n_class_names, d.n_category_names = len(raw0), len(raw1)
+        return d, (raw0, raw1)
+
+    def high_level_row_capacity(self, class_names=None, category_names=None):
+        """afx_batch_high_level_row_capacity: the bytes of text fetch_high_level_row may need for this batch with these names"""
+        d, keep = self._row_desc(None, None, class_names, category_names, 0, 1, True, -1)
+        return int(self.L.afx_batch_high_level_row_capacity(self.h, ctypes.byref(d)))
+
+    def fetch_high_level_row(self, levels=None, class_model=None, category_model=None, class_names=None, category_names=None,
+                             loop_class=0, oneshot_class=1, use_heuristics=True, category_none_class=-1, text=None):
+        """afx_batch_fetch_high_level_row: everything the reference's high-level database stores for every buffer, out of one
+        fetch: "scalars" [n][15], the nine text columns as "text" uint8 [capacity] with "begin" int64 [n][9] and "length"
+        int32 [n][9] (HLR_COLUMNS order) and per column name a list of n bytes objects, and the class decision's "flags" [n],
+        "non_finite" [n], "confidences" [n][2], "status" [n].  class_names / category_names: the models' class names (str or
+        bytes), none without the model.  text: a uint8 array to fill (page-locked memory, say) in place of a new one."""
+        n = self.n_bufs
+        d, keep = self._row_desc(class_model, category_model, class_names, category_names, loop_class, oneshot_class, use_heuristics,
+                                 category_none_class)
+        if text is None:
+            text = np.zeros(max(1, int(self.L.afx_batch_high_level_row_capacity(self.h, ctypes.byref(d)))), dtype=np.uint8)
+        res = {"scalars": np.zeros((n, NUM_HL_SCALARS)), "text": text, "begin": np.zeros((n, len(HLR_COLUMNS)), dtype=np.int64),
+               "length": np.zeros((n, len(HLR_COLUMNS)), dtype=np.int32), "flags": np.zeros(n, dtype=np.int32),
+               "non_finite": np.zeros(n, dtype=np.int32), "confidences": np.zeros((n, 2)), "status": np.zeros(n, dtype=np.int32)}
+        out = _RowOut(text_capacity=text.size)
+        for name, a in res.items():
+            setattr(out, name, a.ctypes.data if a.size else None)
+        info = None
+        if levels is not None:
+            if len(levels) != n:
+                raise ValueError("levels must hold one load info per buffer")
+            info = (_LoadInfo * max(1, n))()
+            for i, lv in enumerate(levels):
+                info[i].peak_value, info[i].rms_value = lv["peak_value"], lv["rms_value"]
+        _check(self.L, self.L.afx_batch_fetch_high_level_row(self.h, info, ctypes.byref(d), ctypes.byref(out)))
+        for c, name in enumerate(HLR_COLUMNS):
             res[name] = [text[res["begin"][i, c]:res["begin"][i, c] + res["length"][i, c]].tobytes() for i in range(n)]
         return res
 

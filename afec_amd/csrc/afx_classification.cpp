@@ -56,26 +56,27 @@ int feature_name(int j, char* dst, size_t cap) {
 namespace afx {
 namespace host {
 
-int launch_features(afx_batch* b, const char* who, const Layout& layout, const FeatureBlock& fb, ResultBlock* rb) {
+bool has_feature_inputs(const afx_batch* b) {
   // a batch keeps AFX_D_STATISTICS apart from its mask: the statistics' device block stands for the bit
   constexpr uint32_t kSeriesBits = AFX_D_CLASSIFICATION_INPUTS & ~(uint32_t)AFX_D_STATISTICS;
-  const int st = reserve_result_block(b, (b->mask & kSeriesBits) == kSeriesBits && (b->n_bufs == 0 || b->d_stats),
-                                      "the batch mask lacks an input of the classification features (AFX_D_CLASSIFICATION_INPUTS)", who, layout, rb);
-  if (st != AFX_OK || rb->n == 0) return st;
-  const size_t n = rb->n;
+  return (b->mask & kSeriesBits) == kSeriesBits && (b->n_bufs == 0 || b->d_stats);
+}
+const char* const kLacksFeatureInputs = "the batch mask lacks an input of the classification features (AFX_D_CLASSIFICATION_INPUTS)";
 
+int enqueue_features(afx_batch* b, const FeatureBlock& fb, const ResultBlock& rb) {
+  const size_t n = rb.n;
   HIP_TRY(hipStreamSynchronize(b->stream));   // the run's effective-length kernel has written d_efflen
   {
     std::vector<double> seconds(n * 3);
     const int lengths = effective_length_seconds(b, seconds.data());
     if (lengths != AFX_OK) return lengths;
-    double* const up12 = at<double>(rb->host, fb.efflen12);
-    double* const up24 = at<double>(rb->host, fb.efflen24);
+    double* const up12 = at<double>(rb.host, fb.efflen12);
+    double* const up24 = at<double>(rb.host, fb.efflen24);
     for (size_t i = 0; i < n; ++i) {
       up12[i] = seconds[i * 3 + 2];
       up24[i] = seconds[i * 3 + 1];
     }
-    std::memcpy(rb->host + fb.status, b->buf_status.data(), n * sizeof(int32_t));
+    std::memcpy(rb.host + fb.status, b->buf_status.data(), n * sizeof(int32_t));
   }
   afx::ClassifyArgs a{};
   a.rec = b->d_rec;
@@ -84,11 +85,17 @@ int launch_features(afx_batch* b, const char* who, const Layout& layout, const F
   a.stats = b->d_stats;
   a.rt_scalars = b->d_rt_scalars;
   a.n_bufs = b->n_bufs;
-  fb.point(&a, rb->dev);
+  fb.point(&a, rb.dev);
 
-  HIP_TRY(hipMemcpyAsync(rb->dev + fb.efflen12, rb->host + fb.efflen12, fb.end - fb.efflen12, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(rb.dev + fb.efflen12, rb.host + fb.efflen12, fb.end - fb.efflen12, hipMemcpyHostToDevice, b->stream));
   HIP_TRY(afx::launch_classification_features(a, b->stream));
   return AFX_OK;
+}
+
+int launch_features(afx_batch* b, const char* who, const Layout& layout, const FeatureBlock& fb, ResultBlock* rb) {
+  const int st = reserve_result_block(b, has_feature_inputs(b), kLacksFeatureInputs, who, layout, rb);
+  if (st != AFX_OK || rb->n == 0) return st;
+  return enqueue_features(b, fb, *rb);
 }
 
 }  // namespace host

@@ -16,11 +16,10 @@ using namespace afx::host;
 namespace afx {
 namespace host {
 
-int launch_high_level_block(afx_batch* b, const char* who, const afx_load_info* levels, const Layout& layout, const HighBlock& hb, ResultBlock* rb) {
-  const int st = reserve_result_block(b, (b->mask & AFX_D_HIGH_LEVEL_INPUTS) == AFX_D_HIGH_LEVEL_INPUTS,
-                                      "the batch mask lacks a series the high-level descriptors read (AFX_D_HIGH_LEVEL_INPUTS)", who, layout, rb);
-  if (st != AFX_OK || rb->n == 0) return st;
+bool has_high_level_inputs(const afx_batch* b) { return (b->mask & AFX_D_HIGH_LEVEL_INPUTS) == AFX_D_HIGH_LEVEL_INPUTS; }
+const char* const kLacksHighLevelInputs = "the batch mask lacks a series the high-level descriptors read (AFX_D_HIGH_LEVEL_INPUTS)";
 
+int enqueue_high_level(afx_batch* b, const afx_load_info* levels, const HighBlock& hb, const ResultBlock& rb) {
   afx::HighArgs a{};
   a.rec = b->d_rec;
   a.lay = b->lay;
@@ -28,18 +27,24 @@ int launch_high_level_block(afx_batch* b, const char* who, const afx_load_info* 
   a.rt_scalars = b->d_rt_scalars;
   a.n_bufs = b->n_bufs;
   a.sample_rate = b->plan->desc.sample_rate;
-  hb.point(&a, rb->dev, levels != nullptr);
+  hb.point(&a, rb.dev, levels != nullptr);
 
   if (levels) {
-    float* const pairs = at<float>(rb->host, hb.levels);
-    for (size_t i = 0; i < rb->n; ++i) {
+    float* const pairs = at<float>(rb.host, hb.levels);
+    for (size_t i = 0; i < rb.n; ++i) {
       pairs[2 * i] = levels[i].peak_value;
       pairs[2 * i + 1] = levels[i].rms_value;
     }
-    HIP_TRY(hipMemcpyAsync(rb->dev + hb.levels, pairs, rb->n * 2 * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(rb.dev + hb.levels, pairs, rb.n * 2 * sizeof(float), hipMemcpyHostToDevice, b->stream));
   }
   HIP_TRY(afx::launch_high_level(a, b->stream));
   return AFX_OK;
+}
+
+int launch_high_level_block(afx_batch* b, const char* who, const afx_load_info* levels, const Layout& layout, const HighBlock& hb, ResultBlock* rb) {
+  const int st = reserve_result_block(b, has_high_level_inputs(b), kLacksHighLevelInputs, who, layout, rb);
+  if (st != AFX_OK || rb->n == 0) return st;
+  return enqueue_high_level(b, levels, hb, *rb);
 }
 
 }  // namespace host

@@ -11,8 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#include "afx_block.h"
-#include "text/afx_text.h"
+#include "afx_text_columns.h"
 
 using namespace afx::host;
 
@@ -50,25 +49,6 @@ struct TextBlock {
   }
 };
 
-// the three columns of every buffer, slot behind slot in the order of AFX_HLT_*; returns the bytes of all slots
-int64_t high_level_columns(const afx_batch* b, afx::TextColumn* table) {
-  constexpr int64_t kSignature = afx::kHighSignatureFrames * afx::kHighSignatureBands;
-  int64_t slot = 0;
-  for (int32_t i = 0; i < b->n_bufs; ++i) {
-    const int64_t row0 = b->frame_offset[(size_t)i], frames = b->frame_offset[(size_t)i + 1] - row0;
-    const afx::TextColumn columns[AFX_NUM_HLT_COLUMNS] = {
-        {(int64_t)i * kSignature, 0, (int32_t)kSignature, afx::kHighSignatureBands}, {row0, 0, (int32_t)frames, 0}, {row0, 0, (int32_t)frames, 0}};
-    for (int c = 0; c < AFX_NUM_HLT_COLUMNS; ++c) {
-      if (table) {
-        table[(size_t)i * AFX_NUM_HLT_COLUMNS + c] = columns[c];
-        table[(size_t)i * AFX_NUM_HLT_COLUMNS + c].slot = slot;
-      }
-      slot += afx::text_slot_bytes(columns[c].count, columns[c].inner);
-    }
-  }
-  return slot;
-}
-
 }  // namespace
 
 extern "C" {
@@ -90,14 +70,10 @@ int afx_batch_fetch_high_level_text(afx_batch* b, const afx_load_info* levels, a
   const int st = launch_high_level_block(b, "afx_batch_fetch_high_level_text", levels, layout, hb, &rb);
   if (st != AFX_OK || rb.n == 0) return st;
 
-  // the columns' values are the block's own arrays: the table's `first` counts doubles from the signature on, behind which
-  // pitch and peak lie (every array of a block starts at a multiple of 8 bytes)
+  // the columns' values are the block's own arrays
   afx::TextColumn* const table = at<afx::TextColumn>(rb.host, tb.columns);
   high_level_columns(b, table);
-  for (size_t i = 0; i < rb.n; ++i) {
-    table[i * AFX_NUM_HLT_COLUMNS + AFX_HLT_PITCH].first += (int64_t)((hb.pitch - hb.signature) / sizeof(double));
-    table[i * AFX_NUM_HLT_COLUMNS + AFX_HLT_PEAK].first += (int64_t)((hb.peak - hb.signature) / sizeof(double));
-  }
+  count_from_signature(table, rb.n, hb);
   HIP_TRY(hipMemcpyAsync(rb.dev + tb.columns, table, tb.begin - tb.columns, hipMemcpyHostToDevice, b->stream));
   afx::TextArgs t{};
   tb.point(&t, rb.dev, at<double>(rb.dev, hb.signature));

@@ -50,6 +50,7 @@ struct TSqliteSampleDescriptorPool::TImpl {
   // prepare it, and look every column up by name.)
   void* mpInsert = nullptr;
   void* mpInsertFailed = nullptr;
+  void* mpInsertClassifier = nullptr;
   enum TSource { kValue, kFileType, kFileSize, kFileLength, kFileSampleRate, kFileChannelCount, kFileBitDepth,
                  kEmptyBlob, kZeroReal, kEmptyText };
   struct TBinding { TSource mSource; int mValueIndex; };
@@ -61,6 +62,16 @@ struct TSqliteSampleDescriptorPool::TImpl {
   void Check(int Result, const char* pWhat) {
     if (Result != kSqliteOk && Result != kSqliteDone)
       throw TReadableException(std::string(pWhat) + ": " + (mpDatabase ? mApi.errmsg(mpDatabase) : "sqlite error"));
+  }
+  void PrepareInsert() {
+    if (mpInsert) return;
+    // SqliteSampleDescriptorPool.cpp:1591-1640: all keys, INSERT OR REPLACE
+    std::string Sql = "INSERT OR REPLACE into assets(filename,modtime,status";
+    for (const TColumnSpec& c : mSchema) Sql += "," + c.mName;
+    Sql += ") values(?,?,?";
+    for (size_t i = 0; i < mSchema.size(); ++i) Sql += ",?";
+    Sql += ")";
+    Check(mApi.prepare_v2(mpDatabase, Sql.c_str(), -1, &mpInsert, nullptr), "prepare");
   }
   void Execute(const std::string& Sql) { Check(mApi.exec(mpDatabase, Sql.c_str(), nullptr, nullptr, nullptr), Sql.c_str()); }
   // first column of the first row as an int (TDatabase::ExecuteScalarInt)
@@ -75,7 +86,12 @@ struct TSqliteSampleDescriptorPool::TImpl {
   }
 };
 
-TSqliteSampleDescriptorPool::TSqliteSampleDescriptorPool(const std::string& DatabasePath, const std::string& Pragmas) : mpImpl(new TImpl) {
+TSqliteSampleDescriptorPool::TSqliteSampleDescriptorPool(const std::string& DatabasePath, const std::string& Pragmas)
+    : TSqliteSampleDescriptorPool(DatabasePath, LowLevelSchema(), false, Pragmas) {}
+
+TSqliteSampleDescriptorPool::TSqliteSampleDescriptorPool(const std::string& DatabasePath, std::vector<TColumnSpec> Schema,
+                                                         bool WithClassesTable, const std::string& Pragmas)
+    : mpImpl(new TImpl) {
   TSqliteApi& A = mpImpl->mApi;
   A.mpLibrary = dlopen("libsqlite3.so.0", RTLD_NOW | RTLD_LOCAL);
   if (!A.mpLibrary) {
@@ -99,7 +115,7 @@ TSqliteSampleDescriptorPool::TSqliteSampleDescriptorPool(const std::string& Data
     Resolve(A.mpLibrary, "sqlite3_errmsg", A.errmsg);
     mpImpl->Check(A.open(DatabasePath.c_str(), &mpImpl->mpDatabase), "sqlite3_open");
     if (!Pragmas.empty()) mpImpl->Execute(Pragmas);
-    mpImpl->mSchema = LowLevelSchema();
+    mpImpl->mSchema = std::move(Schema);
     // TSqliteSampleDescriptorPool::InitializeDatabase (SqliteSampleDescriptorPool.cpp:1224-1358): an existing assets
     // table is kept only at the current version; a newer database is refused, an older one is thrown away
     constexpr int kCurrentVersion = 2;                   // Export/SqliteSampleDescriptorPool.h:58
@@ -121,6 +137,7 @@ TSqliteSampleDescriptorPool::TSqliteSampleDescriptorPool(const std::string& Data
         if (!Pragmas.empty()) mpImpl->Execute(Pragmas);
         if (!DeleteSucceeded) {
           mpImpl->Execute("DROP table 'assets'");
+          mpImpl->Execute("DROP TABLE IF EXISTS classes");
           mpImpl->Execute("VACUUM");
         }
       }
@@ -133,6 +150,8 @@ TSqliteSampleDescriptorPool::TSqliteSampleDescriptorPool(const std::string& Data
       mpImpl->Execute("BEGIN");
       mpImpl->Execute("PRAGMA user_version = '" + std::to_string(kCurrentVersion) + "'");
       mpImpl->Execute(Ddl);
+      // :1352-1358: the high-level database names its classifiers' classes
+      if (WithClassesTable) mpImpl->Execute("CREATE TABLE classes (classifier TEXT PRIMARY KEY, classes BLOB)");
       mpImpl->Execute("COMMIT");
     }
   } catch (...) {
@@ -147,6 +166,7 @@ TSqliteSampleDescriptorPool::~TSqliteSampleDescriptorPool() {
   if (mpImpl->mInTransaction) mpImpl->mApi.exec(mpImpl->mpDatabase, "ROLLBACK", nullptr, nullptr, nullptr);
   if (mpImpl->mpInsert) mpImpl->mApi.finalize(mpImpl->mpInsert);
   if (mpImpl->mpInsertFailed) mpImpl->mApi.finalize(mpImpl->mpInsertFailed);
+  if (mpImpl->mpInsertClassifier) mpImpl->mApi.finalize(mpImpl->mpInsertClassifier);
   mpImpl->mApi.close(mpImpl->mpDatabase);
   dlclose(mpImpl->mApi.mpLibrary);
   delete mpImpl;
@@ -174,15 +194,7 @@ void TSqliteSampleDescriptorPool::InsertSample(const std::string& FileName, int 
 void TSqliteSampleDescriptorPool::InsertColumns(const std::string& FileName, int ModificationTime, const TFileProperties& File,
                                                 const std::vector<TColumn>& Values) {
   TImpl& I = *mpImpl;
-  if (!I.mpInsert) {
-    // SqliteSampleDescriptorPool.cpp:1591-1640: all keys, INSERT OR REPLACE
-    std::string Sql = "INSERT OR REPLACE into assets(filename,modtime,status";
-    for (const TColumnSpec& c : I.mSchema) Sql += "," + c.mName;
-    Sql += ") values(?,?,?";
-    for (size_t i = 0; i < I.mSchema.size(); ++i) Sql += ",?";
-    Sql += ")";
-    I.Check(I.mApi.prepare_v2(I.mpDatabase, Sql.c_str(), -1, &I.mpInsert, nullptr), "prepare");
-  }
+  I.PrepareInsert();
   // the binding table (schema column -> index into Values) is resolved once and reused while Values keeps its shape:
   // the same number of columns and, checked cheaply on every row, the same names where the table points
   bool Resolved = I.mBoundColumnCount == Values.size();
@@ -253,6 +265,68 @@ void TSqliteSampleDescriptorPool::InsertColumns(const std::string& FileName, int
       I.Check(r, "bind");
       ++Index;
     }
+    I.Check(I.mApi.step(pStatement), "insert");
+    I.mApi.reset(pStatement);
+    I.mApi.clear_bindings(pStatement);
+    if (OwnTransaction) I.Execute("COMMIT");
+  } catch (...) {
+    I.mApi.reset(pStatement);
+    I.mApi.clear_bindings(pStatement);
+    I.mApi.exec(I.mpDatabase, "ROLLBACK", nullptr, nullptr, nullptr);
+    I.mInTransaction = false;
+    throw;
+  }
+}
+
+void TSqliteSampleDescriptorPool::InsertBound(const std::string& FileName, int ModificationTime, const TBoundValue* pValues, size_t Count) {
+  TImpl& I = *mpImpl;
+  if (Count != I.mSchema.size()) throw TReadableException("InsertBound: one value per schema column");
+  I.PrepareInsert();
+  const bool OwnTransaction = !I.mInTransaction;
+  if (OwnTransaction) I.Execute("BEGIN");
+  void* const pStatement = I.mpInsert;
+  try {
+    // SQLITE_STATIC (nullptr): the caller's memory is read during the step and released by clear_bindings behind it
+    I.Check(I.mApi.bind_text(pStatement, 1, FileName.c_str(), (int)FileName.size(), nullptr), "bind filename");
+    I.Check(I.mApi.bind_int(pStatement, 2, ModificationTime), "bind modtime");
+    I.Check(I.mApi.bind_text(pStatement, 3, "succeeded", 9, nullptr), "bind status");
+    for (size_t i = 0; i < Count; ++i) {
+      const TBoundValue& v = pValues[i];
+      const int Index = 4 + (int)i;
+      int r = kSqliteOk;
+      switch (v.mKind) {
+        case TBoundValue::kNull: r = I.mApi.bind_null(pStatement, Index); break;
+        case TBoundValue::kText: r = I.mApi.bind_text(pStatement, Index, v.mpText, v.mLength, nullptr); break;
+        case TBoundValue::kInteger: r = I.mApi.bind_int(pStatement, Index, v.mInteger); break;
+        case TBoundValue::kReal: r = I.mApi.bind_double(pStatement, Index, v.mReal); break;
+      }
+      I.Check(r, "bind");
+    }
+    I.Check(I.mApi.step(pStatement), "insert");
+    I.mApi.reset(pStatement);
+    I.mApi.clear_bindings(pStatement);
+    if (OwnTransaction) I.Execute("COMMIT");
+  } catch (...) {
+    I.mApi.reset(pStatement);
+    I.mApi.clear_bindings(pStatement);
+    I.mApi.exec(I.mpDatabase, "ROLLBACK", nullptr, nullptr, nullptr);
+    I.mInTransaction = false;
+    throw;
+  }
+}
+
+void TSqliteSampleDescriptorPool::InsertClassifier(const std::string& ClassifierName, const std::string& ClassesJson) {
+  TImpl& I = *mpImpl;
+  // SqliteSampleDescriptorPool.cpp:1737-1757
+  if (!I.mpInsertClassifier)
+    I.Check(I.mApi.prepare_v2(I.mpDatabase, "INSERT OR REPLACE into classes(classifier, classes) values(?,?)", -1,
+                              &I.mpInsertClassifier, nullptr), "prepare");
+  const bool OwnTransaction = !I.mInTransaction;
+  if (OwnTransaction) I.Execute("BEGIN");
+  void* const pStatement = I.mpInsertClassifier;
+  try {
+    I.Check(I.mApi.bind_text(pStatement, 1, ClassifierName.c_str(), (int)ClassifierName.size(), nullptr), "bind classifier");
+    I.Check(I.mApi.bind_text(pStatement, 2, ClassesJson.c_str(), (int)ClassesJson.size(), nullptr), "bind classes");
     I.Check(I.mApi.step(pStatement), "insert");
     I.mApi.reset(pStatement);
     I.mApi.clear_bindings(pStatement);

@@ -2,7 +2,8 @@
 // TSqliteSampleDescriptorPool (Source/Crawler/FeatureExtraction/Export/SqliteSampleDescriptorPool.h,
 // Source/SqliteSampleDescriptorPool.cpp:1290-1358 tables, 1582-1690 inserts) for the descriptors this
 // library produces.  `PRAGMA user_version = 2`, one `assets` table with the reference's columns; columns of
-// descriptors that are not computed here (rhythm_*) stay NULL.
+// descriptors that are not computed here (rhythm_*) stay NULL.  The second constructor writes the same file format for
+// another schema: the high-level database's (HighLevelPool.h).
 //
 // sqlite is bound at run time (dlopen of libsqlite3.so.0: the image ships the library but not its headers);
 // the constructor throws TReadableException when it is not there.
@@ -30,6 +31,10 @@ public:
   // journal_mode=MEMORY; PRAGMA synchronous=OFF" (rows of ~68 KB otherwise span 17 overflow pages of 4 KB; the
   // rollback journal and the fsync per commit go away) -- the file stays a plain sqlite database with the same table.
   explicit TSqliteSampleDescriptorPool(const std::string& DatabasePath, const std::string& Pragmas = std::string());
+  // The same file format for another set of columns: `Schema` behind filename, modtime and status, and with
+  // WithClassesTable the reference's `classes` table beside `assets` (the high-level database, HighLevelPool.h).
+  TSqliteSampleDescriptorPool(const std::string& DatabasePath, std::vector<TColumnSpec> Schema, bool WithClassesTable,
+                              const std::string& Pragmas = std::string());
   ~TSqliteSampleDescriptorPool();
   TSqliteSampleDescriptorPool(const TSqliteSampleDescriptorPool&) = delete;
   TSqliteSampleDescriptorPool& operator=(const TSqliteSampleDescriptorPool&) = delete;
@@ -49,6 +54,18 @@ public:
   // descriptors (DescriptorColumns.h; any thread), then InsertColumns on the writer.  The row is InsertSample's.
   void InsertColumns(const std::string& FileName, int ModificationTime, const TFileProperties& File,
                      const std::vector<TColumn>& Values);
+  // One value per schema column, in schema order, bound as it lies in the caller's memory (no copy inside sqlite): the
+  // memory has to live until the call returns, not longer.  Status "succeeded".
+  struct TBoundValue {
+    enum TKind { kNull, kText, kInteger, kReal } mKind;
+    const char* mpText;   // kText: mLength bytes, no NUL needed
+    int mLength;
+    int mInteger;         // kInteger
+    double mReal;         // kReal
+  };
+  void InsertBound(const std::string& FileName, int ModificationTime, const TBoundValue* pValues, size_t Count);
+  // INSERT OR REPLACE into the `classes` table of a pool that has one (SqliteSampleDescriptorPool.cpp:1737-1757)
+  void InsertClassifier(const std::string& ClassifierName, const std::string& ClassesJson);
   // the row of a file that could not be analysed: status "error: <Reason>", every descriptor NULL
   void InsertFailedSample(const std::string& FileName, int ModificationTime, const std::string& Reason);
 

@@ -107,6 +107,87 @@ def crawl(images, names=None, devices=(0,), workers=None, files_per_batch=512, d
     return out
 
 
+class HighLevelPool:
+    """The reference's high-level database (afec_amd/host/HighLevelPool.h): an `assets` table with the high-level columns
+    and a `classes` table, written from what Batch.fetch_high_level_row returns."""
+
+    def __init__(self, path, pragmas=None):
+        L = self.L = lib()
+        L.afec_high_level_pool_open.restype = ctypes.c_void_p
+        L.afec_high_level_pool_open.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32]
+        L.afec_high_level_pool_close.restype = None
+        L.afec_high_level_pool_close.argtypes = [ctypes.c_void_p]
+        L.afec_high_level_pool_insert_classifier.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p),
+                                                             ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]
+        L.afec_high_level_pool_insert_rows.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_char_p), ctypes.c_void_p,
+                                                       ctypes.POINTER(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.POINTER(ctypes.c_char_p), ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32]
+        err = ctypes.create_string_buffer(512)
+        self.h = L.afec_high_level_pool_open(str(path).encode(), pragmas.encode() if pragmas else None, err, 512)
+        if not self.h:
+            raise RuntimeError(err.value.decode())
+
+    def insert_classifier(self, classifier, names):
+        """one row of the `classes` table: the classifier's name and its classes' names as a JSON list"""
+        raw = [s.encode() if isinstance(s, str) else bytes(s) for s in names]
+        c_names = (ctypes.c_char_p * max(1, len(raw)))(*raw)
+        err = ctypes.create_string_buffer(512)
+        if self.L.afec_high_level_pool_insert_classifier(self.h, classifier.encode(), c_names, len(raw), err, 512) != 0:
+            raise RuntimeError(err.value.decode())
+
+    def insert_rows(self, file_names, modtimes, files, row, reasons=None):
+        """One fetched batch in one transaction.  files: per file a dict with "type", "size", "length", "sample_rate",
+        "channels", "bit_depth"; row: the dict Batch.fetch_high_level_row returned (or one with the same arrays: "scalars"
+        [n][15], "text" uint8, "begin" / "length" [n][9], and optionally "status", "non_finite" [n]); reasons: per file None
+        or why the caller knows it failed.  -> the number of files recorded as failed (status "error: <reason>")."""
+        from . import capi
+        n = len(file_names)
+        c_names = (ctypes.c_char_p * max(1, n))(*[str(s).encode() for s in file_names])
+        c_types = (ctypes.c_char_p * max(1, n))(*[f["type"].encode() for f in files])
+        c_reasons = None
+        if reasons is not None:
+            c_reasons = (ctypes.c_char_p * max(1, n))(*[r.encode() if r is not None else None for r in reasons])
+        times = np.ascontiguousarray(modtimes, dtype=np.int32).reshape(n)
+        numbers = np.array([[f["size"], f["sample_rate"], f["channels"], f["bit_depth"]] for f in files], dtype=np.int32).reshape(n, 4)
+        lengths = np.array([f["length"] for f in files], dtype=np.float64).reshape(n)
+        keep = {"scalars": np.ascontiguousarray(row["scalars"], dtype=np.float64), "text": np.ascontiguousarray(row["text"], dtype=np.uint8),
+                "begin": np.ascontiguousarray(row["begin"], dtype=np.int64), "length": np.ascontiguousarray(row["length"], dtype=np.int32)}
+        for k in ("status", "non_finite"):
+            if row.get(k) is not None:
+                keep[k] = np.ascontiguousarray(row[k], dtype=np.int32)
+        if keep["scalars"].shape != (n, capi.NUM_HL_SCALARS) or keep["begin"].shape != (n, len(capi.HLR_COLUMNS)) \
+                or keep["length"].shape != keep["begin"].shape or any(a.shape != (n,) for k, a in keep.items() if k in ("status", "non_finite")):
+            raise ValueError("row holds scalars [n][15], begin and length [n][9], status and non_finite [n]")
+        if n and (keep["begin"].min() < 0 or (keep["begin"] + keep["length"]).max() > keep["text"].size or keep["length"].min() < 0):
+            raise ValueError("a column's text leaves the arena")
+        out = capi._RowOut(text_capacity=keep["text"].size)
+        for k, a in keep.items():
+            setattr(out, k, a.ctypes.data if a.size else None)
+        err = ctypes.create_string_buffer(512)
+        rc = self.L.afec_high_level_pool_insert_rows(self.h, n, c_names, times.ctypes.data, c_types, numbers.ctypes.data,
+                                                     lengths.ctypes.data, c_reasons, ctypes.addressof(out), err, 512)
+        if rc < 0:
+            raise RuntimeError(err.value.decode())
+        return rc
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.afec_high_level_pool_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def fill_uniform_mt19937(n, seed):
     """n float32 U(-1, 1) from std::mt19937(seed) + std::uniform_real_distribution<float>(-1, 1): BASELINE configs[1]'s
     generator, the one the CPU-baseline driver (the reference's own objects) draws from."""

@@ -628,6 +628,78 @@ int afx_format_json_g9(const afx_plan* plan, const double* values, int64_t n_val
                        int32_t n_columns, char* text, int64_t text_capacity,
                        int64_t* begin /* [n_columns] */, int32_t* length /* [n_columns] */);
 
+/* ---- the whole high-level row: what the reference's `--level high` run stores per file, out of one fetch ---- *
+ * The nine TEXT columns of the reference's high-level `assets` table and its REAL columns, in the form sqlite binds: the
+ * scalars of afx_batch_fetch_high_level, the three vector columns of afx_batch_fetch_high_level_text, and the class
+ * decision of afx_batch_fetch_class_decision as the text SToJSON makes of it (SqliteSampleDescriptorPool.cpp:316-358,
+ * 884-904), formatted on the GPU (csrc/text/afx_row_text.hip):
+ *   class_signature_VR, class_strengths_VR, category_signature_VR, category_strengths_VR   "[a,b]" of 2 or K numbers, each
+ *       as "%.9g" (the signatures are floats, widened to double as SampleAnalyser.cpp:1097 and 1190 do)
+ *   classes_VS, categories_VS   ["Name","Other"]: the names of the picked indices in pick order, "," alone between them,
+ *       "[]" when nothing was picked.  The reference neither escapes nor quotes inside a name: the bytes are copied.
+ * Without a class model the three class columns are "[]" (SampleAnalyser.cpp:1166-1168), without a category model the
+ * three category columns (:1228-1230).  A buffer the decision gives zeros (no frames, buf_status != 0, non_finite != 0)
+ * has the text of those zeros and "[]" for the picks.
+ * One reservation of the batch's result block, every kernel on the batch's stream, one transfer: the doubles, the features
+ * and the signatures stay on the device.  Every column's text lies in a slot of `text` that depends only on the batch's
+ * frame counts, the models' sizes and the names' lengths (a number column 2 + 17 values bytes, a name column 2 + the sum of
+ * length + 3 over all names); begin[] is the same on every fetch of a batch, what is behind `length` is not written. */
+enum { AFX_HLR_CLASS_SIGNATURE = 0, AFX_HLR_CLASSES, AFX_HLR_CLASS_STRENGTHS, AFX_HLR_CATEGORY_SIGNATURE,
+       AFX_HLR_CATEGORIES, AFX_HLR_CATEGORY_STRENGTHS, AFX_HLR_SPECTRUM_SIGNATURE, AFX_HLR_PITCH, AFX_HLR_PEAK,
+       AFX_NUM_HLR_COLUMNS };                       /* the reference's column order */
+typedef struct {
+  const char* text;                  /* the name's bytes (UTF-8), no NUL needed                                        */
+  int32_t length;                    /* 0..255                                                                         */
+} afx_name;
+typedef struct {
+  afx_decision_desc decision;        /* both models may be NULL: no feature, model or decision kernel is launched then  */
+  const afx_name* class_names;       /* [n_class_names]: "Loop" and "OneShot" at loop_class and oneshot_class           */
+  int32_t n_class_names;             /* 2 with a class model, 0 without                                                 */
+  int32_t n_category_names;          /* the category model's classes, 0 without one                                     */
+  const afx_name* category_names;    /* [n_category_names]                                                              */
+} afx_row_desc;
+typedef struct {
+  double*  scalars;                  /* [n_bufs][AFX_NUM_HL_SCALARS], AFX_HL_* order                                    */
+  char*    text;                     /* [text_capacity], not NUL-terminated                                             */
+  int64_t  text_capacity;
+  int64_t* begin;                    /* [n_bufs][AFX_NUM_HLR_COLUMNS] offsets into text                                 */
+  int32_t* length;                   /* [n_bufs][AFX_NUM_HLR_COLUMNS]                                                   */
+  int32_t* flags;                    /* [n_bufs]: AFX_DECISION_*; 0 without a model                                     */
+  int32_t* non_finite;               /* [n_bufs]: as afx_decision_out; 0 without a model                                */
+  double*  confidences;              /* [n_bufs][2]: as afx_decision_out; -1 without a model                            */
+  int32_t* status;                   /* [n_bufs]: repeats buf_status                                                    */
+} afx_row_out;                       /* scalars, flags, non_finite, confidences and status may be NULL                  */
+/* the text_capacity that is enough for any content of this batch's buffers under `desc`; -1 for a NULL or for names the
+ * fetch would refuse */
+int64_t afx_batch_high_level_row_capacity(const afx_batch* batch, const afx_row_desc* desc);
+/* After afx_batch_run, any number of times.  Synchronous.  AFX_ERR_INVALID_ARG: what afx_batch_fetch_high_level_text and
+ * (with a model) afx_batch_fetch_class_decision refuse; a text_capacity below afx_batch_high_level_row_capacity; more than
+ * 64 names for a model or a name longer than 255 bytes; a name that holds '"', '\' or a byte below 0x20 (the reference
+ * would write text no JSON reader accepts); a name count that is not the model's class count.  Nothing is written then.
+ * AFX_ERR_UNSUPPORTED: a class model with another number of classes than 2. */
+int afx_batch_fetch_high_level_row(afx_batch* batch, const afx_load_info* levels /* [n_bufs] or NULL */, const afx_row_desc* desc,
+                                   afx_row_out* out);
+/* The class columns' kernel on arrays the caller holds (a database's decisions written out again, values no batch
+ * produces).  Not the crawl's path: device memory of its own on the plan's device, the default stream.  Synchronous.
+ * begin and length are [n_files][6] in the order of AFX_HLR_CLASS_SIGNATURE .. AFX_HLR_CATEGORY_STRENGTHS; file i's six
+ * slots start at i x (the bytes of one file's slots), one behind the other.  AFX_ERR_INVALID_ARG: the names as above, a
+ * model's three arrays not all given or all NULL, n_categories outside 2..64 with category arrays, a pick outside
+ * -1 .. count-1 or named twice in a file's list, a capacity below n_files x the bytes of one file's slots. */
+typedef struct {
+  int32_t n_files;
+  int32_t n_categories;              /* K: 2..64 with the category arrays, else ignored                                 */
+  const float* class_signature;      /* [n_files][2]; the three class arrays are all NULL (no class model) or all given */
+  const double* class_strengths;     /* [n_files][2]                                                                    */
+  const int32_t* classes;            /* [n_files][2] picked indices in pick order, -1 padded                            */
+  const float* category_signature;   /* [n_files][K]; likewise all NULL or all given                                    */
+  const double* category_strengths;  /* [n_files][K]                                                                    */
+  const int32_t* categories;         /* [n_files][K]                                                                    */
+  const afx_name* class_names;       /* [2] with the class arrays                                                       */
+  const afx_name* category_names;    /* [K] with the category arrays                                                    */
+} afx_class_json_in;
+int afx_format_class_json(const afx_plan* plan, const afx_class_json_in* in, char* text, int64_t capacity,
+                          int64_t* begin /* [n_files][6] */, int32_t* length /* [n_files][6] */);
+
 /* Page-locked host memory for PCM and result arrays: transfers from / to such buffers run at the
  * host link's rate (pageable memory is staged by the runtime at a fraction of it). */
 void* afx_host_alloc(int64_t bytes);
