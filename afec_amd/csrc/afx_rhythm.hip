@@ -210,7 +210,8 @@ __device__ __forceinline__ void onset_polar_frame(const PCM* xf, double scale, d
   for (int r = 0; r < 16; ++r) p[r].im = xg[(256 - (q + 16 * r)) & 255];
   // kPolarGroup bins at a time (scheduling barriers in between): all sixteen interleaved keep more values alive than
   // there are registers at three waves per SIMD (116 B of scratch).  onset_function_kernel on the C4 share: device library's
-  // atan2 / sqrt 8.60 ms; these with groups of 16 / 8 / 4 / 2 bins: 8.31 / 7.90 / 7.88 / 7.73 ms (tools/ab_rhythm.sh)
+  // atan2 / sqrt 8.60 ms; these with groups of 16 / 8 / 4 / 2 bins: 8.31 / 7.90 / 7.88 / 7.73 ms (the A/B against the
+  // device library is the C4 row of profiles/r03/README.md; the group sizes were taken with the same harness)
   constexpr int kPolarGroup = 2;
 #pragma unroll
   for (int r0 = 0; r0 < 16; r0 += kPolarGroup) {
