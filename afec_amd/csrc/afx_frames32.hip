@@ -7,8 +7,8 @@
 //   load   v[n1] = z[q + 32 n1]                      (hop reuse: rows 0..15 are last frame's 16..31, kept in
 //          registers; the new hop arrives by LDS-DMA in the wave's exchange plane, issued one frame ahead)
 //   P1     32-point DFT over n1, in registers        -> register k1
-//   E      exchange through the wave's LDS plane, slot = 1056 h + 33 k1 + n2 (conflict-free for
-//          ds_write_b64 and ds_read_b64)             -> lane q = k1, register n2
+//   E      exchange through the wave's LDS plane, slot = 1088 h + 34 k1 + n2 (conflict-free for
+//          ds_write_b64 and for ds_read_b128 of the pairs (n2, n2 + 1)) -> lane q = k1, register n2
 //   T      * w1024^(n2 k1)                           (LDS table [n2][k1])
 //   P2     32-point DFT over n2, in registers        -> v[k2] = Z[q + 32 k2]
 //   U      partner Z[1024-k] by a cross-lane read inside the half, even/odd untangle, |X[k]|, k = q + 32 r
@@ -34,11 +34,20 @@ namespace {
 
 using f32x32::cx;
 
-constexpr int kHalfSlots = 1056;                      // 8-byte slots per half: 33 * 31 + 31 + 1, rounded to 32
-constexpr int kPlane32Bytes = 2 * kHalfSlots * 8;     // 16 896 per wave
+constexpr int kRowSlots = 34;                         // 8-byte slots per row k1: even, so that a reader's pairs (n2, n2 + 1) are 16-byte aligned;
+                                                      // 17 sixteen-byte columns a row, so that the 16 lanes of a ds_read_b128 group meet 16 banks
+constexpr int kHalfSlots = kRowSlots * 32;            // 1088 8-byte slots per half
+constexpr int kPlane32Bytes = 2 * kHalfSlots * 8;     // 17 408 per wave: 24 576 of tables + 8 planes = 163 840 bytes, all of a CU's LDS
+constexpr int kMel32Loads = (kMel32Pairs + 1) / 2;    // the packed mel rows come two (filter, row) pairs to a 16-byte load
 constexpr int kWaves32 = 8;   // (six waves with 22.5 KB of LDS each were measured: 5-10 % slower, HISTORY.md round 5)
 // raw sums per frame the statistics / full classes leave for stats32_finish_kernel: sum m, m^2, j m, j^2 m, m^3, m^4,
 // sum log(m + 1e-20), rolloff count, sum x^2 of the hop, max |x| of the hop
+
+// volatile LDS accesses of 8 and 16 bytes: one DS instruction each, in program order (the explicit address space keeps
+// the volatile accesses DS instructions)
+using lds_vdouble = volatile __attribute__((address_space(3))) double;
+typedef double f64x2_t __attribute__((ext_vector_type(2)));
+using lds_vdouble2 = volatile __attribute__((address_space(3))) f64x2_t;
 
 template <int POST_ROWS>
 struct Lds32 {
@@ -58,10 +67,6 @@ typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double2 table_load2(__amdgpu_buffer_rsrc_t rs, int lane_off, int row_off) {
   return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off, row_off, 0));
-}
-// row offset as the scalar offset: for a lane offset the compiler cannot see through
-__device__ __forceinline__ double table_load1(__amdgpu_buffer_rsrc_t rs, int lane_off, int row_off) {
-  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, lane_off, row_off, 0));
 }
 
 // LDS-DMA of one 1 KiB piece (16 bytes per lane: lane L's bytes land at lds_base + IMM + 16 L, read from
@@ -179,8 +184,15 @@ __device__ __forceinline__ double log_lds(double x, const double* c) {
 // log + 14-point DCT-II + store (vector.c:364-391) for the frames whose mel sums sit in lanes 2 f + slot of each
 // half.  recp: this lane's output element of slot s = lane & 1 (coefficient n = (lane >> 1) & 15); left: frames
 // of this half still to be stored, counted from slot s.
+// Every lane needs the 14 logarithms of its frame.  VIA_LDS (MFCC class): each lane writes its logarithm into `bcast`
+// -- 768 bytes of the wave's plane behind the hop image, [half][slot][24] doubles, which that class leaves alone between
+// two exchanges -- and reads its frame's row back as seven 16-byte pairs; the lanes of a slot read the same addresses
+// (a broadcast), the two slots of a ds_read_b128 group lie 12 sixteen-byte columns apart, and the 16 lanes of a
+// ds_write_b64 group store to 8-byte slots f, 24 + f: no bank conflict.  A wave's DS operations execute in order: no
+// barrier.  The other classes, whose upper plane is in use here, gather the values with 28 ds_bpermute_b32.
+template <bool VIA_LDS>
 __device__ __forceinline__ void finish_mfcc32(double acc, double*& recp, int& left, int stride2, const double* dct,
-                                              const double* logc, int lane) {
+                                              const double* logc, int lane, unsigned char* bcast) {
   const double lg = log_lds(fmax(acc, logc[13]), logc);  // XTRACT_LOG_LIMIT 2e-42, vector.c:364
   // lane-derived addresses are recomputed here (laundered lane id): hoisted out of the frame loop they would each
   // hold a register for the whole kernel
@@ -188,16 +200,29 @@ __device__ __forceinline__ void finish_mfcc32(double acc, double*& recp, int& le
   asm volatile("" : "+v"(ln));
   const int n = (ln >> 1) & 15;
   const double2* drow = reinterpret_cast<const double2*>(dct + 16 * (n < kNumCep ? n : 0));
-  const int idx = ((ln & 32) + (ln & 1)) << 2;   // byte index of lane 32 h + s for ds_bpermute
-  const int lo32 = __double2loint(lg), hi32 = __double2hiint(lg);
   double c = 0.0;
+  if constexpr (VIA_LDS) {
+    unsigned char* const row = bcast + 384 * (ln >> 5) + 192 * (ln & 1);
+    *(lds_vdouble*)(row + 8 * n) = lg;
+    lds_vdouble2* const pairs = (lds_vdouble2*)row;
 #pragma unroll
-  for (int m = 0; m < kNumCep; m += 2) {
-    const double2 d = drow[m >> 1];
-    const double l0 = __hiloint2double(__builtin_amdgcn_ds_bpermute(idx + 8 * m, hi32), __builtin_amdgcn_ds_bpermute(idx + 8 * m, lo32));
-    const double l1 = __hiloint2double(__builtin_amdgcn_ds_bpermute(idx + 8 * m + 8, hi32), __builtin_amdgcn_ds_bpermute(idx + 8 * m + 8, lo32));
-    c = fma(l0, d.x, c);
-    c = fma(l1, d.y, c);
+    for (int m = 0; m < kNumCep; m += 2) {
+      const double2 d = drow[m >> 1];
+      const f64x2_t l = pairs[m >> 1];
+      c = fma(l.x, d.x, c);
+      c = fma(l.y, d.y, c);
+    }
+  } else {
+    const int idx = ((ln & 32) + (ln & 1)) << 2;   // byte index of lane 32 h + s for ds_bpermute
+    const int lo32 = __double2loint(lg), hi32 = __double2hiint(lg);
+#pragma unroll
+    for (int m = 0; m < kNumCep; m += 2) {
+      const double2 d = drow[m >> 1];
+      const double l0 = __hiloint2double(__builtin_amdgcn_ds_bpermute(idx + 8 * m, hi32), __builtin_amdgcn_ds_bpermute(idx + 8 * m, lo32));
+      const double l1 = __hiloint2double(__builtin_amdgcn_ds_bpermute(idx + 8 * m + 8, hi32), __builtin_amdgcn_ds_bpermute(idx + 8 * m + 8, lo32));
+      c = fma(l0, d.x, c);
+      c = fma(l1, d.y, c);
+    }
   }
   if (n < kNumCep && left > 0) *recp = c;
   recp += stride2;
@@ -299,25 +324,25 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
   // window and mel tables: buffer loads (one descriptor in SGPRs, lane offset in one VGPR, the row as an
   // immediate / scalar offset) instead of one 64-bit address pair per row
   const __amdgpu_buffer_rsrc_t win_rs = table_rsrc(a.win32, 32 * 32 * 16);                  // [32 n1 + q] double2
-  const __amdgpu_buffer_rsrc_t mel_rs = table_rsrc(a.melw32, kMel32Pairs * 32 * 8);         // [32 pair + q] double
-  const int q16 = 16 * q, q8 = 8 * q;
+  const __amdgpu_buffer_rsrc_t mel_rs = table_rsrc(a.melw32, kMel32Loads * 32 * 16);        // [32 (pair / 2) + q] double2
+  const int q16 = 16 * q;
   const double2* const tw = reinterpret_cast<const double2*>(lds_raw + Map::tw) + q;        // + 32 n2
   const double2* const post = reinterpret_cast<const double2*>(lds_raw + Map::post) + q;    // + 32 r
   const double* const dct = reinterpret_cast<const double*>(lds_raw + Map::dct);
   const double* const logc = reinterpret_cast<const double*>(lds_raw + Map::logc);
   const int stride2 = 2 * a.lay.stride;
   double* const plane = reinterpret_cast<double*>(lds_raw + Map::xchg + wave * kPlane32Bytes) + kHalfSlots * h;
-  double* const pw = plane + q;                      // + 33 k1: this lane is n2 = q when writing
-  // + n2: this lane is k1 = q when reading (volatile: one ds_read_b64 per value, never ds_read2_b64 at half
-  // the rate; the explicit LDS address space keeps the volatile accesses DS instructions)
-  using lds_vdouble = volatile __attribute__((address_space(3))) double;
-  lds_vdouble* const pr = (lds_vdouble*)(plane + 33 * q);
+  double* const pw = plane + q;                      // + 34 k1: this lane is n2 = q when writing
+  // + n2 / 2: this lane is k1 = q when reading, two values (n2, n2 + 1) per 16-byte ds_read_b128 (volatile: one read
+  // per pair, never ds_read2_b64 at half the rate; the explicit LDS address space keeps the volatile accesses DS
+  // instructions)
+  lds_vdouble2* const pr = (lds_vdouble2*)(plane + kRowSlots * q);
   const int partner = (lane & 32) + ((32 - q) & 31);
   // the new hop of the next frame (rows 16..31 of both halves, 8 KiB per wave) is moved global -> LDS by eight
   // global_load_lds_dwordx4 (1 KiB each: lane L's 16 bytes land at 16 L) into the exchange plane, which is idle
   // between two exchanges: image [row][half][q] float2.  Lane L moves complex samples 2 (L & 15), +1 of row
   // 16 + 2 j + (L >> 5) of half (L >> 4) & 1.
-  const int dh = (lane >> 4) & 1, drow = lane >> 5, dq = 2 * (lane & 15);
+  const int dh = (lane >> 4) & 1;
   typedef __attribute__((address_space(3))) void lvoid;
   unsigned char* const plane_bytes = lds_raw + Map::xchg + wave * kPlane32Bytes;
   // the plane's LDS byte address as a wave-uniform scalar (M0 of the DMA)
@@ -344,13 +369,17 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
     const int nfr = have ? ch.nframes : 0;
     const double sc = ch.scale;   // SCALED: FinalScaling of this half's buffer (the arena holds LoadSample's float signal)
     const int total = max(__builtin_amdgcn_readlane(nfr, 0), __builtin_amdgcn_readlane(nfr, 32));
-    const float2* src = reinterpret_cast<const float2*>(pcm + ch.sample_off) + q;
+    // (laundered lane id, as in finish_mfcc32: the lane's share of the three global addresses below is rebuilt for every
+    // chunk pair; hoisted out of this loop each of them held a register pair for the whole kernel)
+    int lc = lane;
+    asm volatile("" : "+v"(lc));
+    const float2* src = reinterpret_cast<const float2*>(pcm + ch.sample_off) + (lc & 31);
     // this lane's part in the LDS-DMA: the chunk of half dh
     const int cid = 2 * slot + dh;
     const bool have_d = cid < a.n_chunks;
     const Chunk chd = a.chunks[have_d ? cid : 2 * slot];
     const int last_d = max((have_d ? (int)chd.nframes : 0) - 1, 0);
-    const float* const dsrc = pcm + chd.sample_off + 64 * (16 + drow) + 2 * dq;   // row 16 + drow, sample 2 dq
+    const float* const dsrc = pcm + chd.sample_off + 64 * (16 + (lc >> 5)) + 4 * (lc & 15);   // row 16 + drow, sample 2 dq
 
     // (pairs of floats as the 8-byte words they are loaded as: an array of float2 was left in scratch memory by the
     // compiler in the larger classes -- 128 bytes per lane stored and reloaded every frame pair)
@@ -367,8 +396,8 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
 
     double mel_acc = 0.0;  // mel sums of up to two finished frames per half: lane 2 f + slot
     // this lane's output element: coefficient (q >> 1) of the frame in slot q & 1
-    double* recp = a.rec + ((int64_t)ch.frame0 + (q & 1)) * a.lay.stride + a.lay.mfcc + ((q >> 1) & 15);
-    int left = nfr - (q & 1);
+    double* recp = a.rec + ((int64_t)ch.frame0 + (lc & 1)) * a.lay.stride + a.lay.mfcc + ((lc >> 1) & 15);
+    int left = nfr - (lc & 1);
 
     // The loop body is software-pipelined by hand (two waves per SIMD leave little for the hardware to hide):
     // every table / LDS / cross-lane read is issued one step before the arithmetic that consumes it, and
@@ -383,14 +412,46 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
     for (int fi = 0; fi < total; ++fi) {
       // ---- window (table carries the 1/2048 of kDivFwdByN and the 1/2 of the untangle) ----
       cx<double> v[32];
-      {
+      auto first = [](double pair) { return __int_as_float(__double2loint(pair)); };
+      auto second = [](double pair) { return __int_as_float(__double2hiint(pair)); };
+      if constexpr (!LO_LDS) {
+        // The overlap half stays in lo's 32 registers from frame to frame, and the new hop is read from the plane INTO
+        // them: rows j, j + 8 are converted and multiplied by their window pairs first (the FFT registers are dead
+        // here), which is the last use of lo's values; the hop read into lo then finishes the first radix-4 stage and
+        // is the next frame's overlap half as it stands.  Per value the operations are those of the other classes'
+        // form below.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the hop's LDS-DMA has landed (and the window pairs)
+        AFX_STAMP(0);   // wait for DMA + window
+        double par[8], pai[8], pbr[8], pbi[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const double ar = pcm_double<SCALED>(first(lo[j]), sc), ai = pcm_double<SCALED>(second(lo[j]), sc);
+          const double br = pcm_double<SCALED>(first(lo[j + 8]), sc), bi = pcm_double<SCALED>(second(lo[j + 8]), sc);
+          par[j] = ar * w[j].x, pai[j] = ai * w[j].y, pbr[j] = br * w[j + 8].x, pbi[j] = bi * w[j + 8].y;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) lo[r] = hop[64 * r];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const double cr = pcm_double<SCALED>(first(lo[j]), sc), ci = pcm_double<SCALED>(second(lo[j]), sc);
+          const double dr = pcm_double<SCALED>(first(lo[j + 8]), sc), di = pcm_double<SCALED>(second(lo[j + 8]), sc);
+          const double t0r = fma(cr, w[j + 16].x, par[j]), t0i = fma(ci, w[j + 16].y, pai[j]);
+          const double t1r = fma(-cr, w[j + 16].x, par[j]), t1i = fma(-ci, w[j + 16].y, pai[j]);
+          const double t2r = fma(dr, w[j + 24].x, pbr[j]), t2i = fma(di, w[j + 24].y, pbi[j]);
+          const double t3r = fma(-dr, w[j + 24].x, pbr[j]), t3i = fma(-di, w[j + 24].y, pbi[j]);
+          v[j] = {t0r + t2r, t0i + t2i};
+          v[j + 16] = {t0r - t2r, t0i - t2i};
+          v[j + 8] = {t1r + t3i, t1i - t3r};
+          v[j + 24] = {t1r - t3i, t1i + t3r};
+        }
+      } else {
         double nx[16];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the hop's LDS-DMA has landed (and the window pairs)
         AFX_STAMP(0);   // wait for DMA + window
 #pragma unroll
         for (int r = 0; r < 16; ++r) nx[r] = hop[64 * r];
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (LO_LDS) {
+        {
           const double* const lo_rows = reinterpret_cast<const double*>(plane_bytes + 8192 + 256 * h) + q;
 #pragma unroll
           for (int r = 0; r < 16; ++r) lo[r] = lo_rows[64 * r];
@@ -400,8 +461,6 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
         double hop_sq = 0.0, hop_max = 0.0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          auto first = [](double pair) { return __int_as_float(__double2loint(pair)); };
-          auto second = [](double pair) { return __int_as_float(__double2hiint(pair)); };
           const double ar = pcm_double<SCALED>(first(lo[j]), sc), ai = pcm_double<SCALED>(second(lo[j]), sc);
           const double br = pcm_double<SCALED>(first(lo[j + 8]), sc), bi = pcm_double<SCALED>(second(lo[j + 8]), sc);
           const double cr = pcm_double<SCALED>(first(nx[j]), sc), ci = pcm_double<SCALED>(second(nx[j]), sc);
@@ -419,10 +478,6 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
           v[j + 16] = {t0r - t2r, t0i - t2i};
           v[j + 8] = {t1r + t3i, t1i - t3r};
           v[j + 24] = {t1r - t3i, t1i + t3r};
-        }
-        if constexpr (!LO_LDS) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) lo[r] = nx[r];
         }
         if constexpr (MAGS) {
           // amplitude_peak / amplitude_rms of the hop, reduced over the half's 32 lanes (magnitude class: no hop_kernel
@@ -473,13 +528,21 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
       {
         double re[32], im[32];
 #pragma unroll
-        for (int k1 = 0; k1 < 32; ++k1) pw[33 * k1] = v[k1].re;
+        for (int k1 = 0; k1 < 32; ++k1) pw[kRowSlots * k1] = v[k1].re;
 #pragma unroll
-        for (int n2 = 0; n2 < 32; ++n2) re[n2] = pr[n2];
+        for (int m = 0; m < 16; ++m) {
+          const f64x2_t two = pr[m];
+          re[2 * m] = two.x;
+          re[2 * m + 1] = two.y;
+        }
 #pragma unroll
-        for (int k1 = 0; k1 < 32; ++k1) pw[33 * k1] = v[k1].im;
+        for (int k1 = 0; k1 < 32; ++k1) pw[kRowSlots * k1] = v[k1].im;
 #pragma unroll
-        for (int n2 = 0; n2 < 32; ++n2) im[n2] = pr[n2];
+        for (int m = 0; m < 16; ++m) {
+          const f64x2_t two = pr[m];
+          im[2 * m] = two.x;
+          im[2 * m + 1] = two.y;
+        }
         load_tw(0);
         load_tw(1);
 #pragma unroll
@@ -514,7 +577,15 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
       double mag[MR];
       cx<double> pp[MR];
       double2 pw2[MR];
-      double mwt[kMel32Pairs];
+      double mwt[2 * kMel32Loads];
+      auto load_mel = [&]() {
+#pragma unroll
+        for (int i = 0; i < kMel32Loads; ++i) {
+          const double2 two = table_load2(mel_rs, q16, 512 * i);
+          mwt[2 * i] = two.x;
+          mwt[2 * i + 1] = two.y;
+        }
+      };
       // statistics class: per-lane partial sums over this lane's bins of the analysis range (bins 1..738, j = bin - 1):
       // sum m, m^2, j m, j^2 m, m^3, m^4 and the product of (m + 1e-20) in two halves (24 factors would underflow)
       double s1 = 0.0, s2 = 0.0, sj = 0.0, sjj = 0.0, s3 = 0.0, s4 = 0.0, prod_a = 1.0, prod_b = 1.0;
@@ -678,8 +749,7 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
           // registers per group; the loads then wait only for the stores issued before them, which are long done when
           // the mel stage starts, and the compiler's wait count lets the later stores stay in flight.
           if (g == kMelEarly) {
-#pragma unroll
-            for (int i = 0; i < kMel32Pairs; ++i) mwt[i] = table_load1(mel_rs, q8, 256 * i);
+            load_mel();
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -721,16 +791,14 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
       // the packed mel rows come from global memory (L1/L2-resident): issued here, when two thirds of the FFT
       // registers are dead
       if (FEAT == 0) {
-#pragma unroll
-        for (int i = 0; i < kMel32Pairs; ++i) mwt[i] = table_load1(mel_rs, q8, 256 * i);
+        load_mel();
       }
 #pragma unroll
       for (int r = 8; r < 12; ++r) untangle(r);
       __builtin_amdgcn_sched_barrier(0);
       }
       if (STATS) {   // statistics class: behind the last rows (62 registers in flight that it cannot spare earlier)
-#pragma unroll
-        for (int i = 0; i < kMel32Pairs; ++i) mwt[i] = table_load1(mel_rs, q8, 256 * i);
+        load_mel();
       }
       AFX_STAMP(6);   // untangle
 
@@ -917,14 +985,14 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
           for (int r = 0; r < 32; ++r) w[r] = table_load2(win_rs, q16, 512 * r);
           if constexpr (LO_LDS) dma_hop<kLoNt>(dsrc + (size_t)min(fi + 1, last_d) * kHop - kHop, plane_lds + 8192);
         }
-        if (fi & 1) finish_mfcc32(mel_acc, recp, left, stride2, dct, logc, lane);
+        if (fi & 1) finish_mfcc32<FEAT == 0>(mel_acc, recp, left, stride2, dct, logc, lane, plane_bytes + 8192);
         AFX_STAMP(9);   // log + DCT + store (every second iteration)
 #if AFX_STAMPS
         stamp_acc[15] += 1;
 #endif
       }
     }
-    if (total & 1) finish_mfcc32(mel_acc, recp, left, stride2, dct, logc, lane);
+    if (total & 1) finish_mfcc32<FEAT == 0>(mel_acc, recp, left, stride2, dct, logc, lane, plane_bytes + 8192);
     unsigned drawn = 0;
     if (lane == 0) drawn = atomicAdd(a.queue, 1u);
     slot = n_static + (int)((unsigned)__builtin_amdgcn_readfirstlane(drawn) - a.queue_base);

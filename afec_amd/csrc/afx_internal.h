@@ -134,7 +134,7 @@ struct FrameArgs {
   const void* win32;   // [32][32] pairs (w[2n], w[2n+1]) / 4096, n = q + 32 n1
   const void* tw32;    // [32][32] complex w1024^(n2 k1), index 32 n2 + k1
   const void* post32;  // [32][32] complex w2048^(q + 32 r)
-  const void* melw32;  // [kMel32Pairs][32] packed mel rows
+  const void* melw32;  // [(kMel32Pairs + 1) / 2][32] double2: packed mel rows, two pairs to a 16-byte load
   unsigned* queue;     // work-queue counter of the half-wave kernels: advances by ceil(n_chunks / 2) per launch
   unsigned queue_base; // its value when this launch starts
   unsigned long long* stamps;   // diagnostic builds (AFX_STAMPS): 16 per-stage cycle counters, else nullptr

@@ -157,12 +157,13 @@ int upload_halfwave_tables(afx_plan* p) {
       tw[32 * r + q] = twiddle<double>((long long)r * q, 1024);   // [n2 = r][k1 = q]
       post[32 * r + q] = twiddle<double>(n, 2048);
     }
-  std::vector<double> melw((size_t)afx::kMel32Pairs * 32, 0.0);
+  // packed mel rows, two (filter, row) pairs to a 16-byte load: [pair / 2][q] double2, the odd last pair next to zeros
+  std::vector<double> melw((size_t)((afx::kMel32Pairs + 1) / 2) * 64, 0.0);
   int idx = 0;
   for (int r = 0; r < afx::kMel32Rows; ++r)
     for (int f = 0; f < afx::kNumCep; ++f)
       if (afx::mel32_touches(f, r)) {
-        for (int q = 0; q < 32; ++q) melw[(size_t)idx * 32 + q] = p->mel[(size_t)f * afx::kHalf + 32 * r + q];
+        for (int q = 0; q < 32; ++q) melw[(size_t)(idx >> 1) * 64 + 2 * q + (idx & 1)] = p->mel[(size_t)f * afx::kHalf + 32 * r + q];
         ++idx;
       }
   auto up = [](void** dst, const void* src, size_t bytes) -> hipError_t {

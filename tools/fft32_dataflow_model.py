@@ -7,7 +7,7 @@ with ONE exchange through LDS:
 
     load   v[n1] = z[q + 32 n1]                      lane q = n2, register n1
     P1     32-point DFT over n1 (registers)           -> register k1
-    E      LDS exchange, slot = 1056 h + 33 k1 + n2   -> lane q = k1, register n2
+    E      LDS exchange, slot = 1088 h + 34 k1 + n2   -> lane q = k1, registers n2, n2 + 1 per 16-byte read
     T      * w1024^(n2 k1)                            (LDS table [n2][k1])
     P2     32-point DFT over n2 (registers)           -> v[k2] = Z[q + 32 k2]
     U      partner Z[1024 - k] from lane (32 - q) & 31, register 31 - r (q = 0: own register (32 - r) & 31),
@@ -20,7 +20,20 @@ numpy; it is a design aid, not part of the product.
 import numpy as np
 
 N = 1024
-HALF_SLOTS = 1056
+ROW_SLOTS = 34             # 8-byte slots per row k1: even (16-byte aligned pairs), 17 sixteen-byte columns a row
+HALF_SLOTS = ROW_SLOTS * 32
+
+
+def write_slots(k1):
+    """8-byte slots the 64 lanes (half h, n2 = q) store register k1 to"""
+    lane = np.arange(64)
+    return HALF_SLOTS * (lane >> 5) + ROW_SLOTS * k1 + (lane & 31)
+
+
+def read_slots(m):
+    """8-byte slots the 64 lanes (half h, k1 = q) read their pair m = (n2, n2 + 1) = (2 m, 2 m + 1) from: even slot first"""
+    lane = np.arange(64)
+    return HALF_SLOTS * (lane >> 5) + ROW_SLOTS * (lane & 31) + 2 * m
 
 
 def w(n, e):
@@ -105,15 +118,16 @@ def fft_wave(za, zb):
     # E: write lane (h, n2 = q) register k1 -> slot; read lane (h, k1 = q) register n2
     plane = np.full(2 * HALF_SLOTS, np.nan + 0j)
     for k1 in range(32):
-        slots = HALF_SLOTS * h + q + 33 * k1
+        slots = write_slots(k1)
         check_write_b64(slots)
         assert np.all(np.isnan(plane[slots].real))
         plane[slots] = B[k1]
     C = np.zeros_like(B)
-    for n2 in range(32):
-        slots = HALF_SLOTS * h + 33 * q + n2
-        check_read_b64(slots)
-        C[n2] = plane[slots]
+    for m in range(16):
+        slots = read_slots(m)
+        assert np.all(slots % 2 == 0)
+        check_read_b128(slots // 2)
+        C[2 * m], C[2 * m + 1] = plane[slots], plane[slots + 1]
     assert not np.any(np.isnan(C.real))
     # T: table [n2][k1], 16-byte entries
     for n2 in range(32):
