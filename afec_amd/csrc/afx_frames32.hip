@@ -11,13 +11,19 @@
 //          ds_write_b64 and for ds_read_b128 of the pairs (n2, n2 + 1)) -> lane q = k1, register n2
 //   T      * w1024^(n2 k1)                           (LDS table [n2][k1])
 //   P2     32-point DFT over n2, in registers        -> v[k2] = Z[q + 32 k2]
-//   U      partner Z[1024-k] by a cross-lane read inside the half, even/odd untangle, |X[k]|, k = q + 32 r
+//   U      partner Z[1024-k] from lane 32 - q of the half (MFCC class: through the wave's plane, 16-byte writes and
+//          reads of {re, im}, bytes [8960, 14080); the other classes: ds_bpermute_b32), even/odd untangle, |X[k]|,
+//          k = q + 32 r
 //
 // then the descriptors straight from the magnitudes in registers; sums over a frame's bins are reductions over
 // the 32 lanes of a half (v_permlane16_swap + DPP), so one instruction stream serves two frames.  Compared with
 // the 64-lane layout of afx_kernels.hip (16 x 4 x 16, two exchanges) this drops the register-transpose exchange
 // (64 v_permlane*_swap per frame), one of the two twiddle stages and half of the reduction work.  Index algebra,
-// LDS bank rules and the reduction's lane map are modelled in tools/fft32_dataflow_model.py.
+// LDS bank rules, the partner image and the reduction's lane map are modelled in tools/fft32_dataflow_model.py.
+//
+// A wave's plane (17 408 bytes) between two exchanges, MFCC class: [0, 8192) the next frame's hop image (LDS-DMA),
+// [8192, 8960) finish_mfcc32's logarithm broadcast, [8960, 14080) the untangle's partner image; the exchange owns all of
+// it.  The other classes keep parked rows and the overlap DMA in the upper half instead.
 //
 // What each stage replaces in the reference (SampleAnalyser.cpp = SA):
 //   window+FFT+magnitude  SA:826-845 (xtract_windowed, TFftTransformComplex, TAudioMath::Magnitude)
@@ -39,6 +45,11 @@ constexpr int kRowSlots = 34;                         // 8-byte slots per row k1
 constexpr int kHalfSlots = kRowSlots * 32;            // 1088 8-byte slots per half
 constexpr int kPlane32Bytes = 2 * kHalfSlots * 8;     // 17 408 per wave: 24 576 of tables + 8 planes = 163 840 bytes, all of a CU's LDS
 constexpr int kMel32Loads = (kMel32Pairs + 1) / 2;    // the packed mel rows come two (filter, row) pairs to a 16-byte load
+// MFCC class: staging area of the untangle's partner rows in the wave's plane, behind the hop image [0, 8192) and the
+// logarithm broadcast [8192, 8960): 5 slots x 2 halves x 512 bytes = [8960, 14080)
+constexpr int kPartnerStage = 8960;
+constexpr int kPartnerSlots = 5;
+static_assert(kPartnerStage + 2 * kPartnerSlots * 512 <= kPlane32Bytes, "the partner staging area lies inside the wave's plane");
 constexpr int kWaves32 = 8;   // (six waves with 22.5 KB of LDS each were measured: 5-10 % slower, HISTORY.md round 5)
 // raw sums per frame the statistics / full classes leave for stats32_finish_kernel: sum m, m^2, j m, j^2 m, m^3, m^4,
 // sum log(m + 1e-20), rolloff count, sum x^2 of the hop, max |x| of the hop
@@ -48,6 +59,7 @@ constexpr int kWaves32 = 8;   // (six waves with 22.5 KB of LDS each were measur
 using lds_vdouble = volatile __attribute__((address_space(3))) double;
 typedef double f64x2_t __attribute__((ext_vector_type(2)));
 using lds_vdouble2 = volatile __attribute__((address_space(3))) f64x2_t;
+using lds_bytes = __attribute__((address_space(3))) unsigned char;
 
 template <int POST_ROWS>
 struct Lds32 {
@@ -113,6 +125,8 @@ __device__ __forceinline__ double mag_sqrt_mel(double xr, double xi, double tiny
   return y * fma(-r, y, three);
 }
 
+// (Classes with the cross-lane partner fetch; the MFCC class needs none of this: its lanes 0 and 32 read their own value
+// back from the partner image.)
 // Lanes 0 and 32 (bins 32 r) are their own partners, at another register than everybody else's: two 64-bit moves
 // under EXEC = {0, 32} put their values in place, instead of four v_cndmask_b32 per row.  EXEC is saved and restored
 // (the kernel's control flow is wave-uniform where this is called, but nothing here depends on that).
@@ -185,8 +199,8 @@ __device__ __forceinline__ double log_lds(double x, const double* c) {
 // half.  recp: this lane's output element of slot s = lane & 1 (coefficient n = (lane >> 1) & 15); left: frames
 // of this half still to be stored, counted from slot s.
 // Every lane needs the 14 logarithms of its frame.  VIA_LDS (MFCC class): each lane writes its logarithm into `bcast`
-// -- 768 bytes of the wave's plane behind the hop image, [half][slot][24] doubles, which that class leaves alone between
-// two exchanges -- and reads its frame's row back as seven 16-byte pairs; the lanes of a slot read the same addresses
+// -- 768 bytes of the wave's plane behind the hop image, [half][slot][24] doubles, bytes [8192, 8960); between two exchanges
+// that class uses the plane above them only for the untangle's partner image, [8960, 14080) -- and reads its frame's row back as seven 16-byte pairs; the lanes of a slot read the same addresses
 // (a broadcast), the two slots of a ds_read_b128 group lie 12 sixteen-byte columns apart, and the 16 lanes of a
 // ds_write_b64 group store to 8-byte slots f, 24 + f: no bank conflict.  A wave's DS operations execute in order: no
 // barrier.  The other classes, whose upper plane is in use here, gather the values with 28 ds_bpermute_b32.
@@ -429,6 +443,8 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
           const double br = pcm_double<SCALED>(first(lo[j + 8]), sc), bi = pcm_double<SCALED>(second(lo[j + 8]), sc);
           par[j] = ar * w[j].x, pai[j] = ai * w[j].y, pbr[j] = br * w[j + 8].x, pbi[j] = bi * w[j + 8].y;
         }
+        // (volatile on purpose: read as 8 ds_read2st64_b64 -- rows 512 bytes apart are exactly that stride -- the loop
+        // measured 0.1 % slower, inside the spread: profiles/r08/ab_partner_plane.txt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) lo[r] = hop[64 * r];
 #pragma unroll
@@ -573,7 +589,7 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
       AFX_STAMP(5);   // P2
 
       // ---- U: untangle + magnitude: mag[r] = |X[q + 32 r]|, four rows at a time, the next four rows' partner
-      // values (cross-lane) and post-twiddles (LDS) in flight ----
+      // values (MFCC class: 16-byte reads of the partner image; the others: cross-lane) and post-twiddles (LDS) in flight ----
       double mag[MR];
       cx<double> pp[MR];
       double2 pw2[MR];
@@ -667,13 +683,46 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
         if (r < 12) prod_a *= f; else prod_b *= f;
         jq += logc[kC32];
       };
+      // MFCC class: the partner rows come through the wave's plane.  The thirteen registers S(0) = v[0], S(s) = v[32 - s]
+      // hold every partner: row r pairs lane q != 0 with S(r + 1) of lane 32 - q and lane 0 with its own S(r).  Every lane
+      // stores S(s) as one 16-byte {re, im} at [half][slot s - 4 b][q] of the staging area behind the logarithm broadcast
+      // (512 bytes a slot, kPartnerSlots slots a half), and reads row r at its own base + 512 (r - 4 b): the base is slot 1,
+      // column 32 - q for q != 0 and slot 0, column 0 for q == 0 -- lanes 0 and 32 read back what they wrote one value
+      // earlier, so no lane is special and there is no EXEC rewrite.  Batch b = rows 4 b .. 4 b + 3 stages S(4 b) .. S(4 b + 4)
+      // in slots 0..4; a wave's DS operations execute in order, so the writes of a batch queue up behind the reads of the
+      // batch before with no wait.  ds_write_b128 is served 8 contiguous lanes (128 contiguous bytes) at a time; the 16-lane
+      // groups of ds_read_b128 meet the 16-byte columns (32 - q) mod 16 and lane 0's column 0 of another slot: 16 different
+      // ones (tools/fft32_dataflow_model.py).  The addresses are rebuilt from a laundered lane id every trip.
+      lds_bytes* stage_w = nullptr;
+      lds_bytes* stage_r = nullptr;
+      if constexpr (FEAT == 0) {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int hq = ln & 31;
+        lds_bytes* const half_stage = (lds_bytes*)plane_bytes + kPartnerStage + kPartnerSlots * 512 * (ln >> 5);
+        stage_w = half_stage + 16 * hq;
+        stage_r = half_stage + (hq ? 1024 - 16 * hq : 0);
+      }
+      auto stage = [&](int b) {
+#pragma unroll
+        for (int j = 0; j < kPartnerSlots; ++j) {
+          const cx<double> s = v[(32 - (4 * b + j)) & 31];
+          *(lds_vdouble2*)(stage_w + 512 * j) = f64x2_t{s.re, s.im};
+        }
+      };
       auto fetch = [&](int r) {
-        pp[r] = {__shfl(v[31 - r].re, partner), __shfl(v[31 - r].im, partner)};
+        if constexpr (FEAT == 0) {
+          const f64x2_t two = *(lds_vdouble2*)(stage_r + 512 * (r & 3));
+          pp[r] = {two.x, two.y};
+        } else {
+          pp[r] = {__shfl(v[31 - r].re, partner), __shfl(v[31 - r].im, partner)};
+        }
         pw2[r] = post[32 * (r % kMel32Rows)];
       };
       auto untangle = [&](int r) {
         cx<double> p = pp[r];
-        keep_lane0(p.re, p.im, v[(32 - r) & 31].re, v[(32 - r) & 31].im, k_lane0);   // q == 0: bin 32 r pairs with this lane's Z[1024 - 32 r]
+        // q == 0: bin 32 r pairs with this lane's Z[1024 - 32 r] (MFCC class: the plane has delivered it)
+        if constexpr (FEAT != 0) keep_lane0(p.re, p.im, v[(32 - r) & 31].re, v[(32 - r) & 31].im, k_lane0);
         const cx<double> z = v[r];
         double2 wq = pw2[r];
         if (r >= kMel32Rows) {   // w2048^(q + 32 r) = w2048^(q + 32 (r - 12)) w2048^384
@@ -775,14 +824,18 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {
+      // (MFCC class: every batch of four rows stages its five partner registers in the plane first)
+      if constexpr (FEAT == 0) stage(0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) fetch(r);
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (FEAT == 0) stage(1);
 #pragma unroll
       for (int r = 4; r < 8; ++r) fetch(r);
 #pragma unroll
       for (int r = 0; r < 4; ++r) untangle(r);
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (FEAT == 0) stage(2);
 #pragma unroll
       for (int r = 8; r < 12; ++r) fetch(r);
 #pragma unroll

@@ -11,7 +11,20 @@ with ONE exchange through LDS:
     T      * w1024^(n2 k1)                            (LDS table [n2][k1])
     P2     32-point DFT over n2 (registers)           -> v[k2] = Z[q + 32 k2]
     U      partner Z[1024 - k] from lane (32 - q) & 31, register 31 - r (q = 0: own register (32 - r) & 31),
-           even/odd untangle, |X[k]| for k = q + 32 r
+           even/odd untangle, |X[k]| for k = q + 32 r.  The MFCC class fetches the partner through the wave's
+           plane (16-byte writes and reads, "partner image" below); the other classes by ds_bpermute_b32.
+
+Partner image (MFCC class, rows r = 0..11).  The 13 registers S(0) = v[0], S(s) = v[32 - s] hold every partner:
+row r pairs lane q != 0 with S(r + 1) of lane 32 - q and lane q == 0 with its own S(r).  Every lane stores S(s) as
+one 16-byte {re, im} at [half][slot][q] (512 B a slot, PARTNER_SLOTS slots a half) and reads row r at
+own_base + 512 (r - first row of the batch), own_base = slot 1, column 32 - q for q != 0 and slot 0, column 0 for
+q == 0: lanes 0 and 32 read back what they wrote one value earlier.  Batch b (rows 4 b .. 4 b + 3) stages
+S(4 b) .. S(4 b + 4) in slots 0..4 -- neighbouring batches share one value -- and a wave's DS operations execute in
+order, so a batch's writes follow the reads of the batch before without a wait.  Bytes of a wave's plane between
+two exchanges (the exchange itself owns all 17 408):
+    [0, 8192)       hop image, written by the LDS-DMA issued behind the exchange, read at the top of the next trip
+    [8192, 8960)    logarithm broadcast of finish_mfcc32, every second trip, behind the untangle
+    [8960, 14080)   partner image, written and read by the untangle
 
 then the mel sums reduced over the 32 lanes of the half (v_permlane16_swap + DPP).  This script checks
 the index algebra, the LDS bank rules (MI355X_MICROARCH.md, LDS section) and the reduction's lane map against
@@ -64,6 +77,94 @@ def check_read_b128(slots16):
         addr = slots16[g]
         uniq = np.unique(addr)
         assert len(set((uniq % 16).tolist())) == len(uniq), ("b128 conflict", g)
+
+
+PLANE_BYTES = 2 * HALF_SLOTS * 8          # 17 408 per wave
+HOP_IMAGE = (0, 8192)                     # LDS-DMA target: [row][half][q] float2
+LOG_BCAST = (8192, 8960)                  # finish_mfcc32: [half][slot][24] doubles
+PARTNER_STAGE = 8960                      # partner image: [half][slot][q] {re, im}
+PARTNER_SLOTS = 5
+PARTNER_ROWS = 12
+PARTNER_BATCH_ROWS = 4
+PARTNER_IMAGE = (PARTNER_STAGE, PARTNER_STAGE + 2 * PARTNER_SLOTS * 512)
+
+
+def partner_register(s):
+    """register of P2's output that holds value S(s), s = 0..12"""
+    return 0 if s == 0 else 32 - s
+
+
+def partner_write_addr(slot):
+    """byte addresses (in the wave's plane) the 64 lanes store a value of slot `slot` to: 16 bytes each"""
+    lane = np.arange(64)
+    return PARTNER_STAGE + PARTNER_SLOTS * 512 * (lane >> 5) + 512 * slot + 16 * (lane & 31)
+
+
+def partner_read_addr(r):
+    """byte addresses the 64 lanes read row r's partner from: own base + 512 (r - first row of the batch)"""
+    lane = np.arange(64)
+    q = lane & 31
+    base = np.where(q != 0, 512 + 16 * (32 - q), 0)
+    return PARTNER_STAGE + PARTNER_SLOTS * 512 * (lane >> 5) + base + 512 * (r % PARTNER_BATCH_ROWS)
+
+
+def partner_program():
+    """the untangle's DS operations on the partner image in program order: ("w", s, slot) stores S(s), ("r", r) reads
+    row r's partner"""
+    ops = []
+    for b in range(PARTNER_ROWS // PARTNER_BATCH_ROWS):
+        ops += [("w", PARTNER_BATCH_ROWS * b + j, j) for j in range(PARTNER_SLOTS)]
+        ops += [("r", PARTNER_BATCH_ROWS * b + i) for i in range(PARTNER_BATCH_ROWS)]
+    return ops
+
+
+def partner_needs(r):
+    """(value s, source lane) each of the 64 lanes needs for row r"""
+    lane = np.arange(64)
+    q = lane & 31
+    s = np.where(q != 0, r + 1, r)
+    src = (lane & 32) + ((32 - q) & 31)
+    return s, src
+
+
+def check_write_b128(addr):
+    """ds_write_b128: 8 groups of 8 contiguous lanes, bank = (addr / 4) mod 32, four banks a lane: the 16-byte columns
+    mod 8 must be distinct inside a group."""
+    assert np.all(addr % 16 == 0)
+    for g in range(0, 64, 8):
+        c = (addr[g:g + 8] // 16) % 8
+        assert len(set(c.tolist())) == 8, ("b128 write conflict", g, c)
+
+
+def run_partner_image(D=None):
+    """Plays partner_program() on a byte-addressed image of the plane, 16-byte cells tagged (s, lane) (and holding
+    D[register][lane] when D is given).  Checks alignment, bounds, both bank rules and that every read finds the value the
+    untangle needs -- that is, no write has replaced a value a later read still wants.  Returns {r: partner values}."""
+    cells = {}
+    out = {}
+    for op in partner_program():
+        if op[0] == "w":
+            _, s, slot = op
+            addr = partner_write_addr(slot)
+            assert addr.min() >= PARTNER_IMAGE[0] and addr.max() + 16 <= PARTNER_IMAGE[1] <= PLANE_BYTES
+            check_write_b128(addr)
+            for l, a in enumerate(addr.tolist()):
+                cells[a] = (s, l, None if D is None else D[partner_register(s)][l])
+        else:
+            r = op[1]
+            addr = partner_read_addr(r)
+            assert np.all(addr % 16 == 0)
+            assert addr.min() >= PARTNER_IMAGE[0] and addr.max() + 16 <= PARTNER_IMAGE[1]
+            check_read_b128(addr // 16)
+            s, src = partner_needs(r)
+            vals = []
+            for l, a in enumerate(addr.tolist()):
+                assert a in cells, ("read of a cell never written", r, l)
+                assert cells[a][:2] == (s[l], src[l]), ("wrong partner", r, l, cells[a][:2], (s[l], src[l]))
+                vals.append(cells[a][2])
+            out[r] = None if D is None else np.array(vals)
+    assert sorted(out) == list(range(PARTNER_ROWS))
+    return out
 
 
 def swap16(x, y):
@@ -145,15 +246,20 @@ def fft_wave(za, zb):
     return D, Z
 
 
-def untangle(D, rows):
-    """|X[k]| for k = q + 32 r from the registers of P2 (windowed input carries the 1/2)."""
+def untangle(D, rows, via_plane=False):
+    """|X[k]| for k = q + 32 r from the registers of P2 (windowed input carries the 1/2).  via_plane: the partners of
+    rows 0..11 come through the partner image (MFCC class) instead of the cross-lane read."""
     lane = np.arange(64)
     h, q = lane >> 5, lane & 31
     partner = 32 * h + ((32 - q) & 31)
     mag = np.zeros((rows, 64))
+    image = run_partner_image(D) if via_plane else {}
     for r in range(rows):
         p = D[31 - r][partner]
         p = np.where(q == 0, D[(32 - r) & 31], p)
+        if r in image:
+            assert np.array_equal(image[r], p), r
+            p = image[r]
         z = D[r]
         wk = w(2048, q + 32 * r)
         E = z + np.conj(p)
@@ -176,6 +282,10 @@ def main():
         for r in range(32):
             got[32 * r:32 * r + 32] = mag[r][32 * hh:32 * hh + 32]
         assert np.max(np.abs(got - ref)) < 1e-9, np.max(np.abs(got - ref))
+    # the partner image of the MFCC class delivers the same partners, bit for bit, on conflict-free addresses
+    assert np.array_equal(untangle(D, PARTNER_ROWS, via_plane=True), mag[:PARTNER_ROWS])
+    for lo, hi in (HOP_IMAGE, LOG_BCAST):
+        assert hi <= PARTNER_IMAGE[0] or PARTNER_IMAGE[1] <= lo
     # reduction lane map
     lane = np.arange(64)
     a = [rng.uniform(0, 1, 64) for _ in range(16)]
@@ -183,7 +293,7 @@ def main():
     for l in range(64):
         hh, f = l >> 5, (l & 31) >> 1
         assert abs(z[l] - a[f][32 * hh:32 * hh + 32].sum()) < 1e-12, l
-    print("fft32 dataflow model OK: FFT, untangle, LDS bank rules, half-wave reduction")
+    print("fft32 dataflow model OK: FFT, untangle, partner image, LDS bank rules, half-wave reduction")
 
 
 if __name__ == "__main__":
