@@ -36,85 +36,6 @@ double CpuSeconds(clockid_t Clock) {
 double ProcessCpuSeconds() { return CpuSeconds(CLOCK_PROCESS_CPUTIME_ID); }
 double ThreadCpuSeconds() { return CpuSeconds(CLOCK_THREAD_CPUTIME_ID); }
 
-// 64-bit FNV-1a over 8-byte words (row digests: equality of results, not cryptography)
-struct TDigest {
-  uint64_t mHash = 1469598103934665603ull;
-  void Add(const void* p, size_t Bytes) {
-    const unsigned char* b = (const unsigned char*)p;
-    size_t i = 0;
-    for (; i + 8 <= Bytes; i += 8) {
-      uint64_t w;
-      std::memcpy(&w, b + i, 8);
-      mHash = (mHash ^ w) * 1099511628211ull;
-    }
-    for (; i < Bytes; ++i) mHash = (mHash ^ b[i]) * 1099511628211ull;
-  }
-};
-
-// page-locked host memory (afx_host_alloc), grown on demand
-struct TPinned {
-  void* mp = nullptr;
-  size_t mBytes = 0;
-  ~TPinned() { afx_host_free(mp); }
-  // at least Bytes, keeping the first Used bytes of what is there
-  void Reserve(size_t Bytes, size_t Used = 0) {
-    if (Bytes <= mBytes) return;
-    const size_t NewBytes = Bytes + Bytes / 4;
-    if (!Used) { afx_host_free(mp); mp = nullptr; mBytes = 0; }   // nothing to keep: let go of the old block first
-    void* pNew = afx_host_alloc((int64_t)NewBytes);
-    if (!pNew) throw TReadableException("page-locked host memory exhausted");
-    if (Used) std::memcpy(pNew, mp, Used);
-    afx_host_free(mp);
-    mp = pNew;
-    mBytes = NewBytes;
-  }
-};
-
-// page-locking memory costs milliseconds per allocation: result buffers are recycled between the workers (which fill
-// them) and the writer (which lets go of them).  A pooled buffer goes back to the pool it came from when its owner
-// lets go of it, on every path: the pools hand out unique_ptrs whose deleter is the pool's Release.
-template <class TPool>
-struct TBackTo {
-  TPool* mpPool = nullptr;
-  template <class T> void operator()(T* p) const { mpPool->Release(std::unique_ptr<T>(p)); }
-};
-
-class TPinnedPool {
-public:
-  using TLease = std::unique_ptr<TPinned, TBackTo<TPinnedPool>>;
-  TLease Acquire(size_t Bytes) {
-    TLease p(nullptr, {this});
-    {
-      std::lock_guard<std::mutex> Lock(mMutex);
-      // the smallest free buffer that is large enough, else the largest one (it is grown)
-      size_t Best = mFree.size();
-      for (size_t i = 0; i < mFree.size(); ++i) {
-        const bool Fits = mFree[i]->mBytes >= Bytes;
-        if (Best == mFree.size()) Best = i;
-        else {
-          const bool BestFits = mFree[Best]->mBytes >= Bytes;
-          if ((Fits && (!BestFits || mFree[i]->mBytes < mFree[Best]->mBytes)) || (!Fits && !BestFits && mFree[i]->mBytes > mFree[Best]->mBytes)) Best = i;
-        }
-      }
-      if (Best < mFree.size()) {
-        p.reset(mFree[Best].release());
-        mFree.erase(mFree.begin() + (long)Best);
-      }
-    }
-    if (!p) p.reset(new TPinned);
-    p->Reserve(Bytes);
-    return p;
-  }
-  void Release(std::unique_ptr<TPinned> p) {
-    std::lock_guard<std::mutex> Lock(mMutex);
-    mFree.push_back(std::move(p));
-  }
-
-private:
-  std::mutex mMutex;
-  std::vector<std::unique_ptr<TPinned>> mFree;
-};
-
 // The column values of a batch's files (461 per file, ~68 KB of msgpack for a one-second file), built by the worker that
 // analysed the batch so that the one writer thread only binds and steps; recycled between batches: names and BLOB
 // capacities persist (RefillLowLevelColumns)
@@ -142,15 +63,13 @@ private:
 };
 
 // what a worker hands to the writer: one analysed batch (its result buffers travel with it)
-struct TFinishedBatch {
-  std::vector<const TCrawlFile*> mFiles;
-  std::vector<TFileProperties> mProperties;
-  std::vector<std::string> mFailed;          // non-empty: the file is a failed sample with this reason
-  std::vector<char> mSkipped;                // 1: not analysed and not recorded (sampling rate other than the analyser's)
-  std::vector<int> mBatchIndex;              // file -> index inside mResults, -1 for files that never reached the GPU
+struct TFinishedBatch : TCrawlBatch {
   TRecordBatch mResults;
   TPinnedPool::TLease mpRecords, mpStatistics, mpRhythm;
   TRowSetPool::TLease mpRows;                // with a database: mRows[k] = the column values of batch file k
+  // with a mode (TCrawlOptions::mpMode) in place of the four above: what its fetch kept, the batch's frames, the bytes that came back
+  std::unique_ptr<TCrawlBatchResult> mpModeResult;
+  int64_t mModeFrames = 0, mModeResultBytes = 0;
 };
 
 class TBoundedQueue {
@@ -193,6 +112,7 @@ struct TCrawlerState {
   int mSampleRate, mFftFrameSize, mHopFrameSize;
   std::vector<std::unique_ptr<TSampleAnalyser>> mAnalysers;
   TPinnedPool mRecordPool, mStatisticsPool, mRhythmPool, mStagingPool;   // one pool per kind of buffer: nothing regrows
+  TPinnedPool mModePool;   // the buffers of a mode's fetches (TCrawlMode::Fetch)
   TRowSetPool mRowPool;
   int mHardwareQueuesInEnvironment = 0;
 };
@@ -243,13 +163,19 @@ public:
   const int mG, mW;   // devices, worker threads per device
   TCrawlRun(TCrawlerState& Crawler, const std::vector<TCrawlFile>& Files, const TCrawlOptions& Options)
       : mG((int)Options.mDevices.size()), mW(Options.mWorkersPerDevice < 1 ? WorkersPerDeviceFor(mG) : Options.mWorkersPerDevice),
-        mOptions(Options), mpFirstFile(Files.data()),
+        mOptions(Options), mpMode(Options.mpMode.get()), mWithDatabase(!Options.mDatabasePath.empty()), mpFirstFile(Files.data()),
         mFilesPerBatch(Options.mFilesPerBatch < 1 ? 1 : Options.mFilesPerBatch),
         mBytesPerBatch(Options.mBytesPerBatch < 1 ? 1 : Options.mBytesPerBatch),
         mDeviceBytesPerBatch(Options.mDeviceBytesPerBatch < 1 ? 1 : Options.mDeviceBytesPerBatch), mShard((size_t)mG),
         mCrawler(Crawler), mCursor((size_t)mG, 0), mCursorMutex((size_t)mG),
         mFaultBudget(Options.mTestFailAttempts < 0 ? (1 << 30) : Options.mTestFailAttempts), mQueue((size_t)(2 * mG * mW)) {
-    if (!Options.mDatabasePath.empty()) mpDatabase.reset(new TSqliteSampleDescriptorPool(Options.mDatabasePath, Options.mDatabasePragmas));
+    if (mpMode) {
+      std::vector<const TSampleAnalyser*> Analysers;
+      for (const std::unique_ptr<TSampleAnalyser>& p : Crawler.mAnalysers) Analysers.push_back(p.get());
+      mpMode->Begin(Analysers, Options.mDatabasePath, Options.mDatabasePragmas);
+    } else if (mWithDatabase) {
+      mpDatabase.reset(new TSqliteSampleDescriptorPool(Options.mDatabasePath, Options.mDatabasePragmas));
+    }
     for (size_t i = 0; i < Files.size(); ++i) mShard[(size_t)ShardOfFile((int64_t)i, mG)].push_back(&Files[i]);
     mTotal.mFilesPerDevice.assign((size_t)mG, 0);
     mTotal.mPcmBytesPerDevice.assign((size_t)mG, 0);
@@ -296,7 +222,7 @@ public:
       std::lock_guard<std::mutex> Lock(mStatMutex);
       mTotal.mFailedFiles += Failed;
       mTotal.mSkippedSampleRateFiles += Skipped;
-      if (mpDatabase) mTotal.mWriterSeconds += Now() - t0;
+      if (mWithDatabase) mTotal.mWriterSeconds += Now() - t0;
       mPhaseCpuSeconds[2] += ThreadCpuSeconds() - c0;
     }
   }
@@ -422,6 +348,7 @@ private:
         AnalyseOnDevice(d, Work);
       } catch (const TReadableException& e) {
         Done.mResults = TRecordBatch();
+        Done.mpModeResult.reset();
         if (mOptions.mTestDeviceLost || !mCrawler.mAnalysers[(size_t)d]->DeviceUsable()) throw;   // nothing more can be analysed: the crawl ends
         {
           std::lock_guard<std::mutex> Lock(mStatMutex);
@@ -476,6 +403,14 @@ private:
     TFinishedBatch& Done = *Work.mpDone;
     if (Work.mOrdinal == mOptions.mTestFailBatch && mFaultBudget.fetch_sub(1) > 0)
       throw TReadableException("GPU feature extraction failed: injected fault (TCrawlOptions::mTestFailBatch)");
+    if (mpMode) {
+      // the mode's descriptors alone; what comes back is the mode's fetch, into buffers of the crawler's
+      Analyser.AnalyzeAndHandOver(Decoded, mpMode->Mask(), [&](const TRunBatch& Batch) {
+        Done.mModeFrames = Batch.mFrames;
+        Done.mpModeResult = mpMode->Fetch(d, Batch, mCrawler.mModePool, Done.mModeResultBytes);
+      }, Done.mResults.mSeconds);
+      return;
+    }
     TPinnedPool::TLease pRecords;
     TPinnedPool::TLease pStatistics = mCrawler.mStatisticsPool.Acquire(
         Decoded.size() * (size_t)TSampleAnalyser::kMaxStride * TSampleAnalyser::kStatisticsPerSeries * sizeof(double));
@@ -502,6 +437,14 @@ private:
   void FinishBatch(TWork& Work) {
     TFinishedBatch& Done = *Work.mpDone;
     const TRecordBatch& R = Done.mResults;
+    if (mpMode) {
+      // what becomes of a file on the device is the mode's to say (TCrawlMode::Write); the digests are taken here, by the workers
+      if (mOptions.mRowDigests)
+        for (size_t i = 0; i < Done.mFiles.size(); ++i)
+          if (Done.mBatchIndex[i] >= 0 && Done.mFailed[i].empty())
+            mTotal.mRowDigests[(size_t)(Done.mFiles[i] - mpFirstFile)] = mpMode->DigestOf(*Done.mpModeResult, Done.mBatchIndex[i]);
+      return;
+    }
     // with a database: the rows' column values are built here, by the eight workers, not by the one writer
     if (mpDatabase) {
       Done.mpRows = mCrawler.mRowPool.Acquire();
@@ -525,7 +468,10 @@ private:
     const int64_t n = (int64_t)Work.mpDone->mFiles.size(), Analysed = (int64_t)Work.mDecoded.size();
     int64_t Frames = 0, ResultBytes = 0, PcmBytes = 0;
     for (const TDecodedSample& s : Work.mDecoded) PcmBytes += s.mNumberOfSampleFrames * s.mNumberOfChannels * BytesPerSample(s.mFormat);
-    if (Analysed) {
+    if (Analysed && mpMode) {
+      Frames = Work.mpDone->mModeFrames;
+      ResultBytes = Work.mpDone->mModeResultBytes;
+    } else if (Analysed) {
       Frames = R.mFrameOffset.back();
       ResultBytes = (Frames * R.mStride + Analysed * R.mStride * TSampleAnalyser::kStatisticsPerSeries + R.mRhythmOffset.back() * 2 +
                      Analysed * TSampleAnalyser::kRhythmDoublesPerFile) * (int64_t)sizeof(double);
@@ -550,6 +496,7 @@ private:
   // (Until round 5 the loop also broke when another thread set mAbort mid-batch, and the commit then committed the
   // partial batch.)
   void WriteBatch(const TFinishedBatch& Batch, int64_t& Failed, int64_t& Skipped) {
+    if (mpMode) { mpMode->Write(Batch, Batch.mpModeResult.get(), Failed, Skipped); return; }
     if (mpDatabase) mpDatabase->BeginTransaction();     // one commit per batch of files; the rows are those of one commit per file
     for (size_t i = 0; i < Batch.mFiles.size(); ++i) {
       const TCrawlFile& f = *Batch.mFiles[i];
@@ -578,6 +525,8 @@ private:
 
   // ---- immutable once the constructor has run
   const TCrawlOptions& mOptions;
+  TCrawlMode* const mpMode;             // nullptr: the low-level crawl.  Write is the writer thread's, Fetch and DigestOf are const
+  const bool mWithDatabase;
   const TCrawlFile* const mpFirstFile;
   const int mFilesPerBatch;
   const int64_t mBytesPerBatch, mDeviceBytesPerBatch;
@@ -669,6 +618,11 @@ TCrawlStatistics TCrawler::Crawl(const std::vector<TCrawlFile>& Files, const TCr
   if (Options.mDevices != mpImpl->mDevices || Options.mSampleRate != mpImpl->mSampleRate ||
       Options.mFftFrameSize != mpImpl->mFftFrameSize || Options.mHopFrameSize != mpImpl->mHopFrameSize)
     throw TReadableException("TCrawler::Crawl: devices / geometry differ from the crawler's");
+  // a mode is told that the crawl has ended on every way out, also when it did not start
+  struct TModeEnd {
+    TCrawlMode* mp;
+    ~TModeEnd() { if (mp) mp->End(); }
+  } ModeEnd{Options.mpMode.get()};
   TCrawlRun Run(*mpImpl, Files, Options);
   std::thread Writer(&TCrawlRun::WriterLoop, &Run);
   std::vector<std::thread> Workers;
@@ -714,72 +668,97 @@ extern "C" void afec_crawl_set_database_pragmas(const char* pragmas) {
   gDatabasePragmas = pragmas ? pragmas : "";
 }
 
+namespace afec {
+
+std::vector<TCrawlFile> CrawlFilesOf(const char* const* names, const void* const* images, const int64_t* sizes, int32_t n_files) {
+  std::vector<TCrawlFile> Files((size_t)(n_files < 0 ? 0 : n_files));
+  for (int32_t i = 0; i < n_files; ++i) {
+    Files[(size_t)i].mFileName = names[i];
+    Files[(size_t)i].mModificationTime = 1700000000 + i;
+    Files[(size_t)i].mpImage = images ? images[i] : nullptr;
+    Files[(size_t)i].mImageSize = images ? (size_t)sizes[i] : 0;
+  }
+  return Files;
+}
+
+TCrawlOptions CrawlOptionsFromSetters(const int32_t* devices, int32_t n_devices, int32_t workers_per_device, int32_t files_per_batch,
+                                      const char* database_path, bool row_digests) {
+  TCrawlOptions Options;
+  Options.mDevices.assign(devices, devices + n_devices);
+  if (workers_per_device > 0) Options.mWorkersPerDevice = workers_per_device;
+  if (files_per_batch > 0) Options.mFilesPerBatch = files_per_batch;
+  if (database_path) Options.mDatabasePath = database_path;
+  if (gBytesPerBatch > 0) Options.mBytesPerBatch = gBytesPerBatch;
+  Options.mResample = gResample;
+  Options.mTestFailBatch = gTestFailBatch; Options.mTestFailAttempts = gTestFailAttempts; Options.mTestDeviceLost = gTestDeviceLost != 0;
+  if (gDeviceBytesPerBatch > 0) Options.mDeviceBytesPerBatch = gDeviceBytesPerBatch;
+  if (gFrameKernel >= 0) Options.mFrameKernel = gFrameKernel;
+  Options.mRowDigests = row_digests;
+  Options.mpAbortRequested = &gAbortRequested;
+  {
+    std::lock_guard<std::mutex> Lock(gPragmaMutex);
+    Options.mDatabasePragmas = gDatabasePragmas;
+  }
+  return Options;
+}
+
+TCrawlStatistics CrawlOnKeptCrawler(const std::vector<TCrawlFile>& Files, const TCrawlOptions& Options) {
+  // one crawler per (devices, geometry), kept between calls
+  // (the registry lock is held for the whole crawl: afec_crawl_release cannot delete a crawler that is in use, and
+  // crawls through this entry point run one at a time)
+  std::lock_guard<std::mutex> Lock(gCrawlerMutex);
+  gAbortRequested = false;
+  TCrawler* pCrawler = nullptr;
+  {
+    std::string Key;
+    for (int d : Options.mDevices) Key += std::to_string(d) + ",";
+    Key += "k" + std::to_string(Options.mFrameKernel);   // a crawler keeps the kernel layout its plans were built with
+    for (auto& Entry : gCrawlers)
+      if (Entry.first == Key) pCrawler = Entry.second;
+    if (!pCrawler) {
+      pCrawler = new TCrawler(Options);
+      gCrawlers.emplace_back(Key, pCrawler);
+    }
+  }
+  return pCrawler->Crawl(Files, Options);
+}
+
+void StoreCrawlStatistics(const TCrawlStatistics& s, int32_t n_files, int32_t n_devices, double* stats, double* device_stats,
+                          uint64_t* row_digests, double* crawl_facts) {
+  if (stats) {
+    stats[0] = (double)s.mFiles; stats[1] = (double)s.mFailedFiles; stats[2] = (double)s.mFrames; stats[3] = (double)s.mPcmBytes;
+    stats[4] = (double)s.mResultBytes; stats[5] = s.mSeconds; stats[6] = s.mWriterSeconds;
+    stats[7] = (double)s.mBatches;
+    for (int32_t d = 0; d < n_devices; ++d) stats[8 + d] = (double)s.mFilesPerDevice[(size_t)d];
+    stats[8 + n_devices] = s.mCpuSeconds;
+    stats[9 + n_devices] = (double)s.mSkippedSampleRateFiles;
+    stats[10 + n_devices] = (double)s.mRetriedBatches;
+    stats[11 + n_devices] = (double)s.mDeviceFailedFiles;
+  }
+  if (device_stats)
+    for (int32_t d = 0; d < n_devices; ++d) {
+      device_stats[3 * d] = (double)s.mFilesPerDevice[(size_t)d];
+      device_stats[3 * d + 1] = (double)s.mPcmBytesPerDevice[(size_t)d];
+      device_stats[3 * d + 2] = s.mSecondsPerDevice[(size_t)d];
+    }
+  if (row_digests)
+    for (int32_t i = 0; i < n_files; ++i) row_digests[i] = s.mRowDigests[(size_t)i];
+  if (crawl_facts) { crawl_facts[0] = (double)s.mWorkersPerDevice; crawl_facts[1] = s.mUsableHostCpus; crawl_facts[2] = s.mAborted ? 1.0 : 0.0; }
+}
+
+}  // namespace afec
+
 extern "C" int afec_crawl_wave_images_ex(const char* const* names, const void* const* images, const int64_t* sizes,
                                          int32_t n_files, const int32_t* devices, int32_t n_devices, int32_t workers_per_device,
                                          int32_t files_per_batch, const char* database_path, double* stats,
                                          double* device_stats, uint64_t* row_digests, double* crawl_facts, char* error,
                                          int32_t error_size) {
   try {
-    std::vector<afec::TCrawlFile> Files((size_t)n_files);
-    for (int32_t i = 0; i < n_files; ++i) {
-      Files[(size_t)i].mFileName = names[i];
-      Files[(size_t)i].mModificationTime = 1700000000 + i;
-      Files[(size_t)i].mpImage = images ? images[i] : nullptr;
-      Files[(size_t)i].mImageSize = images ? (size_t)sizes[i] : 0;
-    }
-    afec::TCrawlOptions Options;
-    Options.mDevices.assign(devices, devices + n_devices);
-    if (workers_per_device > 0) Options.mWorkersPerDevice = workers_per_device;
-    if (files_per_batch > 0) Options.mFilesPerBatch = files_per_batch;
-    if (database_path) Options.mDatabasePath = database_path;
-    if (gBytesPerBatch > 0) Options.mBytesPerBatch = gBytesPerBatch;
-    Options.mResample = gResample;
-    Options.mTestFailBatch = gTestFailBatch; Options.mTestFailAttempts = gTestFailAttempts; Options.mTestDeviceLost = gTestDeviceLost != 0;
-    if (gDeviceBytesPerBatch > 0) Options.mDeviceBytesPerBatch = gDeviceBytesPerBatch;
-    if (gFrameKernel >= 0) Options.mFrameKernel = gFrameKernel;
-    Options.mRowDigests = row_digests != nullptr;
-    Options.mpAbortRequested = &gAbortRequested;
-    {
-      std::lock_guard<std::mutex> Lock(gPragmaMutex);
-      Options.mDatabasePragmas = gDatabasePragmas;
-    }
-    // one crawler per (devices, geometry), kept between calls
-    // (the registry lock is held for the whole crawl: afec_crawl_release cannot delete a crawler that is in use, and
-    // crawls through this entry point run one at a time)
-    std::lock_guard<std::mutex> Lock(gCrawlerMutex);
-    gAbortRequested = false;
-    afec::TCrawler* pCrawler = nullptr;
-    {
-      std::string Key;
-      for (int d : Options.mDevices) Key += std::to_string(d) + ",";
-      Key += "k" + std::to_string(Options.mFrameKernel);   // a crawler keeps the kernel layout its plans were built with
-      for (auto& Entry : gCrawlers)
-        if (Entry.first == Key) pCrawler = Entry.second;
-      if (!pCrawler) {
-        pCrawler = new afec::TCrawler(Options);
-        gCrawlers.emplace_back(Key, pCrawler);
-      }
-    }
-    const afec::TCrawlStatistics s = pCrawler->Crawl(Files, Options);
-    if (stats) {
-      stats[0] = (double)s.mFiles; stats[1] = (double)s.mFailedFiles; stats[2] = (double)s.mFrames; stats[3] = (double)s.mPcmBytes;
-      stats[4] = (double)s.mResultBytes; stats[5] = s.mSeconds; stats[6] = s.mWriterSeconds;
-      stats[7] = (double)s.mBatches;
-      for (int32_t d = 0; d < n_devices; ++d) stats[8 + d] = (double)s.mFilesPerDevice[(size_t)d];
-      stats[8 + n_devices] = s.mCpuSeconds;
-      stats[9 + n_devices] = (double)s.mSkippedSampleRateFiles;
-      stats[10 + n_devices] = (double)s.mRetriedBatches;
-      stats[11 + n_devices] = (double)s.mDeviceFailedFiles;
-    }
-    if (device_stats)
-      for (int32_t d = 0; d < n_devices; ++d) {
-        device_stats[3 * d] = (double)s.mFilesPerDevice[(size_t)d];
-        device_stats[3 * d + 1] = (double)s.mPcmBytesPerDevice[(size_t)d];
-        device_stats[3 * d + 2] = s.mSecondsPerDevice[(size_t)d];
-      }
-    if (row_digests)
-      for (int32_t i = 0; i < n_files; ++i) row_digests[i] = s.mRowDigests[(size_t)i];
-    if (crawl_facts) { crawl_facts[0] = (double)s.mWorkersPerDevice; crawl_facts[1] = s.mUsableHostCpus; crawl_facts[2] = s.mAborted ? 1.0 : 0.0; }
+    const std::vector<afec::TCrawlFile> Files = afec::CrawlFilesOf(names, images, sizes, n_files);
+    const afec::TCrawlOptions Options =
+        afec::CrawlOptionsFromSetters(devices, n_devices, workers_per_device, files_per_batch, database_path, row_digests != nullptr);
+    const afec::TCrawlStatistics s = afec::CrawlOnKeptCrawler(Files, Options);
+    afec::StoreCrawlStatistics(s, n_files, n_devices, stats, device_stats, row_digests, crawl_facts);
     return 0;
   } catch (const std::exception& e) {
     if (error && error_size > 0) std::snprintf(error, (size_t)error_size, "%s", e.what());

@@ -13,24 +13,86 @@
 //     mSleepingWaits);
 //   * results come back as the raw per-frame records and statistics (one transfer each, afx_batch_fetch_records)
 //     and go through a bounded queue to ONE writer, which materialises TSampleDescriptors per file and inserts them
-//     into the reference's `assets` table (TSqliteSampleDescriptorPool) -- or just counts them.
+//     into the reference's `assets` table (TSqliteSampleDescriptorPool) -- or just counts them;
+//   * what is fetched from a batch and what the writer stores is a mode (TCrawlMode): the above is the low-level one, the
+//     reference's default `--level high` crawl is HighLevelCrawler.h.
 #pragma once
 
 #include <atomic>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "PinnedPool.h"
 #include "SampleAnalyser.h"
+#include "SqlitePool.h"
 
 namespace afec {
+
+// 64-bit FNV-1a over 8-byte words (row digests: equality of results, not cryptography)
+struct TDigest {
+  uint64_t mHash = 1469598103934665603ull;
+  void Add(const void* p, size_t Bytes) {
+    const unsigned char* b = (const unsigned char*)p;
+    size_t i = 0;
+    for (; i + 8 <= Bytes; i += 8) {
+      uint64_t w;
+      std::memcpy(&w, b + i, 8);
+      mHash = (mHash ^ w) * 1099511628211ull;
+    }
+    for (; i < Bytes; ++i) mHash = (mHash ^ b[i]) * 1099511628211ull;
+  }
+};
 
 struct TCrawlFile {
   std::string mFileName;            // the database key (the crawler stores paths relative to the crawl root)
   int mModificationTime = 0;
   const void* mpImage = nullptr;    // the file's bytes when it is already in memory; nullptr: read mFileName
   size_t mImageSize = 0;
+};
+
+// The host side of one analysed batch, as a worker hands it to the writer: the files it was cut with and what became of
+// each before and on the device.  Batch file k is the k-th file whose mBatchIndex is not -1.
+struct TCrawlBatch {
+  std::vector<const TCrawlFile*> mFiles;
+  std::vector<TFileProperties> mProperties;
+  std::vector<std::string> mFailed;          // non-empty: the file is a failed sample with this reason
+  std::vector<char> mSkipped;                // 1: not analysed and not recorded (sampling rate other than the analyser's)
+  std::vector<int> mBatchIndex;              // file -> index inside the device batch, -1 for files that never reached the GPU
+};
+
+// what a mode's worker fetched from a device batch; travels to the writer with the batch
+struct TCrawlBatchResult {
+  virtual ~TCrawlBatchResult() = default;
+};
+
+// What a crawl computes per file and where it stores it (TCrawlOptions::mpMode).  Cutting batches, staging, the retry in
+// halves, fault injection, abort, accounting and the bounded queue are the run's (Crawler.cpp) and serve every mode; a mode
+// says which descriptors a batch computes, what a worker fetches from it and what the writer does with that.  The run
+// calls the virtuals below and nothing else of a mode, so a mode may use fetches and pools that Crawler.cpp does not link
+// against (HighLevelCrawler.h).  One crawl at a time per mode object.
+class TCrawlMode {
+public:
+  virtual ~TCrawlMode() = default;
+  // the AFX_D_* bits of every batch of the crawl
+  virtual uint32_t Mask() const = 0;
+  // Once per crawl, on the caller's thread, before any file is read: Analysers[d] serves TCrawlOptions::mDevices[d] (per
+  // device state -- models -- is created here), then the database, if DatabasePath is not empty, is opened and whatever
+  // precedes the first batch is written.  Throws TReadableException: the crawl does not start.
+  virtual void Begin(const std::vector<const TSampleAnalyser*>& Analysers, const std::string& DatabasePath,
+                     const std::string& DatabasePragmas) = 0;
+  // A worker of device index d, any number at once: what the crawl keeps of a batch that has run.  Buffers: page-locked
+  // memory that outlives the crawl (the result may hold a lease).  ResultBytes: what came back from the device.
+  virtual std::unique_ptr<TCrawlBatchResult> Fetch(int d, const TRunBatch& Batch, TPinnedPool& Buffers, int64_t& ResultBytes) const = 0;
+  // the digest of batch file k (TCrawlOptions::mRowDigests), 0 for a file the writer will record as failed
+  virtual uint64_t DigestOf(const TCrawlBatchResult& Result, int k) const = 0;
+  // The writer thread: one finished batch, whole or not at all.  pResult: nullptr when none of its files reached the
+  // device.  Failed / Skipped: the files it recorded as failed / left out.  Without a database the files are counted.
+  virtual void Write(const TCrawlBatch& Batch, const TCrawlBatchResult* pResult, int64_t& Failed, int64_t& Skipped) = 0;
+  // the crawl has ended, however: the database is closed, per-device state is let go of
+  virtual void End() noexcept = 0;
 };
 
 struct TCrawlOptions {
@@ -86,6 +148,9 @@ struct TCrawlOptions {
   // once it reads true; batches already analysed are delivered and written whole, the crawl returns normally with
   // TCrawlStatistics::mAborted set and mFiles counting what was done.  nullptr: the crawl cannot be aborted from outside.
   const std::atomic<bool>* mpAbortRequested = nullptr;
+  // What is computed and stored per file.  nullptr: the low-level crawl -- every per-frame record and its statistics into
+  // the low-level database (TSqliteSampleDescriptorPool).  HighLevelCrawler.h has the reference's default, `--level high`.
+  std::shared_ptr<TCrawlMode> mpMode;
 };
 
 // CPUs the process may use at once: the cgroup CPU bandwidth quota (v2 cpu.max, v1 cfs_quota_us / cfs_period_us) where
@@ -100,7 +165,7 @@ struct TCrawlStatistics {
   // (neither analysed nor written as failed samples: a later crawl finds them missing, not broken)
   int64_t mSkippedSampleRateFiles = 0;
   int64_t mPcmBytes = 0;            // bytes of PCM uploaded
-  int64_t mResultBytes = 0;         // bytes of records + statistics downloaded
+  int64_t mResultBytes = 0;         // bytes of records + statistics downloaded (with a mode: what its fetches brought back)
   double mSeconds = 0;              // first file read .. last result delivered to the writer
   double mWriterSeconds = 0;        // time the writer spent inserting (0 without a database)
   std::vector<int64_t> mFilesPerDevice;
@@ -141,6 +206,19 @@ private:
   struct TImpl;
   std::unique_ptr<TImpl> mpImpl;
 };
+
+// ---- what afec_crawl_wave_images_ex does around the crawl itself, for the C entry points of modes in other files ----
+// file i of a C caller: names[i], modification time 1700000000 + i, images[i] / sizes[i] unless images is NULL
+std::vector<TCrawlFile> CrawlFilesOf(const char* const* names, const void* const* images, const int64_t* sizes, int32_t n_files);
+// TCrawlOptions as the arguments and the process-wide setters (afec_crawl_set_*, afec_crawl_request_abort) give them
+TCrawlOptions CrawlOptionsFromSetters(const int32_t* devices, int32_t n_devices, int32_t workers_per_device, int32_t files_per_batch,
+                                      const char* database_path, bool row_digests);
+// Crawl on the process' crawler for Options' devices and kernel layout (built on first use, kept until
+// afec_crawl_release); crawls through it run one at a time
+TCrawlStatistics CrawlOnKeptCrawler(const std::vector<TCrawlFile>& Files, const TCrawlOptions& Options);
+// the statistics in the layout afec_crawl_wave_images_ex documents; any pointer may be NULL
+void StoreCrawlStatistics(const TCrawlStatistics& s, int32_t n_files, int32_t n_devices, double* stats, double* device_stats,
+                          uint64_t* row_digests, double* crawl_facts);
 
 }  // namespace afec
 

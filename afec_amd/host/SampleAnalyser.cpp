@@ -112,13 +112,14 @@ std::vector<TSampleDataInfo> InfoOf(const std::vector<afx_load_info>& Info) {
 }
 
 // decoded files -> a batch whose LoadSample front end has run; Info[i] is what it found
-void CreateFromFiles(afx_plan* pPlan, const std::vector<TDecodedSample>& Files, TBatchGuard& Batch, std::vector<afx_load_info>& Info) {
+void CreateFromFiles(afx_plan* pPlan, const std::vector<TDecodedSample>& Files, TBatchGuard& Batch, std::vector<afx_load_info>& Info,
+                     uint32_t Mask = kEverything) {
   std::vector<afx_raw> Raws(Files.size());
   for (size_t i = 0; i < Files.size(); ++i)
     Raws[i] = {Files[i].mpInterleavedSamples, Files[i].mFormat, Files[i].mNumberOfChannels, Files[i].mSampleRate, 0,
                Files[i].mNumberOfSampleFrames};
   Info.resize(Files.size());
-  const int Status = afx_batch_create_from_raw(pPlan, Raws.data(), (int32_t)Files.size(), kEverything, &Batch.mpBatch, Info.data());
+  const int Status = afx_batch_create_from_raw(pPlan, Raws.data(), (int32_t)Files.size(), Mask, &Batch.mpBatch, Info.data());
   if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
 }
 
@@ -249,6 +250,22 @@ bool TSampleAnalyser::AnalyzeToRecords(const std::vector<TDecodedSample>& Files,
   RunAndFetch(Batch.mpBatch, (int32_t)Files.size(), &Files, Info, mSampleRate, pRecords, pStatistics, pRhythm, Result);
   Result.mSeconds[0] = t1 - t0;
   return true;
+}
+
+void TSampleAnalyser::AnalyzeAndHandOver(const std::vector<TDecodedSample>& Files, uint32_t Mask,
+                                         const std::function<void(const TRunBatch&)>& Fetch, double* pSeconds) const {
+  TBatchGuard Batch;
+  std::vector<afx_load_info> Info;
+  const double t0 = Now();
+  CreateFromFiles(mpPlan, Files, Batch, Info, Mask);
+  const double t1 = Now();
+  int Status = SetFileInfo(Batch.mpBatch, Files, Info, mSampleRate);
+  if (Status == AFX_OK) Status = afx_batch_run(Batch.mpBatch);
+  if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);
+  const double t2 = Now();
+  const std::vector<TSampleDataInfo> Facts = InfoOf(Info);
+  Fetch(TRunBatch{Batch.mpBatch, Info.data(), Facts, afx_batch_total_frames(Batch.mpBatch)});
+  if (pSeconds) { pSeconds[0] = t1 - t0; pSeconds[1] = t2 - t1; pSeconds[2] = Now() - t2; }
 }
 
 TSampleDescriptors TSampleAnalyser::AnalyzeLowLevelDescriptors(const std::vector<double>& SampleData,

@@ -10,6 +10,7 @@
 
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -109,6 +110,15 @@ struct TRecordBatch {
   TSampleDescriptors Descriptors(int FileIndex) const;
 };
 
+// A batch that has run (afx_batch_run), as TSampleAnalyser::AnalyzeAndHandOver hands it to its caller: whatever is
+// fetched from it is the caller's business.  Valid while the call runs.
+struct TRunBatch {
+  afx_batch* mpBatch;
+  const afx_load_info* mpLevels;               // [files]: what the LoadSample front end found (the fetches' `levels`)
+  const std::vector<TSampleDataInfo>& mInfo;   // [files]: the same as TRecordBatch::mInfo carries it
+  int64_t mFrames;                             // afx_batch_total_frames
+};
+
 class TSampleAnalyser {
 public:
   // Device: HIP device ordinal.  FrameKernel: afx_plan_desc.frame_kernel -- the layout of the STFT kernel, PINNED by
@@ -160,6 +170,14 @@ public:
   static int64_t ConvertedSampleFrames(const TDecodedSample& File, int Rate);   // sample frames once the file is at Rate
   bool AnalyzeToRecords(const std::vector<TDecodedSample>& Files, double* pRecords, size_t RecordCapacity,
                         double* pStatistics, double* pRhythm, size_t RhythmCapacity, TRecordBatch& Batch) const;
+
+  // What AnalyzeToRecords does up to and including afx_batch_run, for the descriptors of Mask (AFX_D_*) alone; the batch
+  // then goes to Fetch, which takes from it what it wants, and is destroyed when Fetch returns or throws.  pSeconds
+  // (nullptr or [3]): wall time of upload + LoadSample, kernels enqueue, Fetch -- TRecordBatch::mSeconds.
+  void AnalyzeAndHandOver(const std::vector<TDecodedSample>& Files, uint32_t Mask, const std::function<void(const TRunBatch&)>& Fetch,
+                          double* pSeconds = nullptr) const;
+  // the analyser's plan: models (afx_model_create_from_lightgbm) are created per plan.  The analyser keeps owning it.
+  afx_plan* Plan() const { return mpPlan; }
 
 private:
   afx_plan* mpPlan;

@@ -25,6 +25,43 @@ def _bind(L):
     return L
 
 
+class _ModelSpec(ctypes.Structure):
+    """afec_model_spec of afec_amd/host/HighLevelCrawler.h"""
+    _fields_ = [("texts", ctypes.POINTER(ctypes.c_char_p)), ("lens", ctypes.POINTER(ctypes.c_size_t)), ("n_models", ctypes.c_int32),
+                ("scale", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("limits", ctypes.c_void_p),
+                ("early_stop_freq", ctypes.c_int32), ("early_stop_margin", ctypes.c_double),
+                ("names", ctypes.POINTER(ctypes.c_char_p)), ("name_lens", ctypes.POINTER(ctypes.c_int32)), ("n_names", ctypes.c_int32)]
+
+
+def _bind_high_level(L):
+    """the high-level crawl's entry point: bound when it is used (a host library without HighLevelCrawler.cpp -- the mock
+    device's -- still serves every other call)"""
+    L.afec_crawl_high_level_ex.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_void_p),
+                                           ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p,
+                                           ctypes.POINTER(_ModelSpec), ctypes.POINTER(_ModelSpec), ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
+                                           ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int32]
+    return L.afec_crawl_high_level_ex
+
+
+def _model_spec(model):
+    """a model dict (texts, scale, offset, limits, names; optionally early_stop_freq, early_stop_margin) -> (_ModelSpec,
+    what it points to).  Nothing is checked here: the library refuses what it cannot use."""
+    texts = [t.encode() if isinstance(t, str) else bytes(t) for t in model["texts"]]
+    names = [s.encode() if isinstance(s, str) else bytes(s) for s in model["names"]]
+    vectors = [None if model[k] is None else np.ascontiguousarray(model[k], dtype=np.float64).reshape(-1) for k in ("scale", "offset", "limits")]
+    if any(v is not None and v.size != 1680 for v in vectors):
+        raise ValueError("scale, offset and limits hold 1680 values each")
+    keep = [texts, names, vectors, (ctypes.c_char_p * max(1, len(texts)))(*texts), (ctypes.c_size_t * max(1, len(texts)))(*[len(t) for t in texts]),
+            (ctypes.c_char_p * max(1, len(names)))(*names), (ctypes.c_int32 * max(1, len(names)))(*[len(s) for s in names])]
+    spec = _ModelSpec(texts=keep[3], lens=keep[4], n_models=len(texts), scale=None if vectors[0] is None else vectors[0].ctypes.data,
+                      offset=None if vectors[1] is None else vectors[1].ctypes.data, limits=None if vectors[2] is None else vectors[2].ctypes.data,
+                      early_stop_freq=int(model.get("early_stop_freq", 10)), early_stop_margin=float(model.get("early_stop_margin", 10.0)),
+                      names=keep[5], name_lens=keep[6], n_names=len(names))
+    return spec, keep
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -64,10 +101,28 @@ def wave_probe_file(path):
 
 
 def crawl(images, names=None, devices=(0,), workers=None, files_per_batch=512, database=None, digests=False):
-    """images: list of bytes (WAV file images), or None: names are the paths of files on disk.  -> dict of statistics.
+    """The low-level crawl: every per-frame record and its statistics into the low-level database.  images: list of bytes (WAV file images), or None: names are the paths of files on disk.  -> dict of statistics.
     workers: host threads per device; None = the library's choice (TCrawlOptions::mWorkersPerDevice = 0: from the CPUs the
     process may use and the number of devices, at most 5).  digests: also "row_digests", one uint64 per file over
     everything the device returned for it (0: not analysed)."""
+    return _crawl(images, names, devices, workers, files_per_batch, database, digests, None)
+
+
+def crawl_high_level(images, names=None, devices=(0,), workers=None, files_per_batch=512, database=None, digests=False,
+                     class_model=None, category_model=None, category_none_class=-1, use_heuristics=True):
+    """The reference's default crawl (`--level high`, afec_amd/host/HighLevelCrawler.h): the same run as crawl() -- streaming,
+    sharded, retried in halves -- into the high-level database: an `assets` row per file with the high-level columns and a
+    `classes` table that names the models' classes.  A model is a dict with "texts" (the members' LightGBM texts), "scale",
+    "offset", "limits" ([1680] each) and "names" (its classes' names), as models.read_reference_model returns it; None: the
+    reference's `--model none`, the model's three columns are "[]".  category_none_class: the index of the category model's
+    "None" class, or -1.  -> the statistics of crawl(); "result_bytes" counts what the row fetches brought back, a file's
+    digest covers its row."""
+    return _crawl(images, names, devices, workers, files_per_batch, database, digests,
+                  {"class_model": class_model, "category_model": category_model, "category_none_class": category_none_class,
+                   "use_heuristics": use_heuristics})
+
+
+def _crawl(images, names, devices, workers, files_per_batch, database, digests, high_level):
     L = lib()
     n = len(images) if images is not None else len(names)
     names = names or [f"file{i:06d}.wav" for i in range(n)]
@@ -85,11 +140,18 @@ def crawl(images, names=None, devices=(0,), workers=None, files_per_batch=512, d
     facts = (ctypes.c_double * 3)()
     row_digests = np.zeros(n, dtype=np.uint64) if digests else None
     err = ctypes.create_string_buffer(512)
-    rc = L.afec_crawl_wave_images_ex(c_names, c_images, c_sizes, n, c_dev, G, int(workers or 0), files_per_batch,
-                                     database.encode() if database else None, stats, device_stats,
-                                     row_digests.ctypes.data if digests else None, facts, err, 512)
+    if high_level is None:
+        rc = L.afec_crawl_wave_images_ex(c_names, c_images, c_sizes, n, c_dev, G, int(workers or 0), files_per_batch,
+                                         database.encode() if database else None, stats, device_stats,
+                                         row_digests.ctypes.data if digests else None, facts, err, 512)
+    else:
+        specs = [_model_spec(m) if m is not None else (None, None) for m in (high_level["class_model"], high_level["category_model"])]
+        rc = _bind_high_level(L)(c_names, c_images, c_sizes, n, c_dev, G, int(workers or 0), files_per_batch,
+                                  database.encode() if database else None, specs[0][0], specs[1][0],
+                                  int(high_level["category_none_class"]), 1 if high_level["use_heuristics"] else 0, stats,
+                                  device_stats, row_digests.ctypes.data if digests else None, facts, err, 512)
     if rc != 0:
-        raise RuntimeError(err.value.decode())
+        raise RuntimeError(err.value.decode(errors="replace"))
     keys = ["files", "failed", "frames", "pcm_bytes", "result_bytes", "seconds", "writer_seconds", "batches"]
     out = dict(zip(keys, list(stats)[:8]))
     out["files_per_device"] = [int(v) for v in list(stats)[8:8 + G]]
