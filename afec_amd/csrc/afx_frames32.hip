@@ -61,11 +61,10 @@ typedef double f64x2_t __attribute__((ext_vector_type(2)));
 using lds_vdouble2 = volatile __attribute__((address_space(3))) f64x2_t;
 using lds_bytes = __attribute__((address_space(3))) unsigned char;
 
-template <int POST_ROWS>
 struct Lds32 {
   static constexpr int tw = 0;                              // [32][32] cx<double>: w1024^(n2 k1)
-  static constexpr int post = tw + 32 * 32 * 16;            // [POST_ROWS][32] cx<double>: w2048^(q + 32 r)
-  static constexpr int dct = post + POST_ROWS * 32 * 16;    // [14][16] double
+  static constexpr int post = tw + 32 * 32 * 16;            // [kMel32Rows][32] cx<double>: w2048^(q + 32 r), the untangle factors of rows 0..11; rows 12..15 are rows 0..3 times w2048^384
+  static constexpr int dct = post + kMel32Rows * 32 * 16;   // [14][16] double
   static constexpr int logc = dct + 14 * 16 * 8;            // 32 doubles: constants of the logarithm and of the statistics (kLogConst)
   static constexpr int xchg = logc + 32 * 8;                // kWaves32 planes
   static constexpr int total = xchg + kWaves32 * kPlane32Bytes;
@@ -261,61 +260,383 @@ __device__ __forceinline__ void finish_mfcc32(double acc, double*& recp, int& le
 #define AFX_STAMP(i)
 #endif
 
-// Statistics class: untangle the bins in PAIRS.  X[k] and X[1024 - k] come from the same (Z[k], Z[1024 - k]):
-// X[k] = E + w O, |X[1024 - k]| = |E - w O|, so row r (bins 32 r + q) also yields the "mirrored block" M_r = bins
-// 32 (31 - r) + 1 .. 32 (32 - r) -- in reversed lane order (lane q holds bin 1024 - 32 r - q; lane 0 the block's last
-// bin) -- for ten more operations instead of a second fetch + untangle.  Rows 0..15, bin 512 (lane 0 of row 16, its own
-// partner) and M_15..M_8 cover the analysis range 1..738: 16 untangle steps instead of 24.
+// The seven feature classes (FEAT) of frames32_kernel.  frames32_class() maps a mask to 0..4; launch_frames32 picks 5 and 6.
+//
+//   FEAT  masks                                          leaves                                            finished by
+//   0     MFCC alone (mask == 1)                         MFCC                                              --
+//   1     + spectral statistics (bits 1..7 only)         MFCC, raw sums in a.stat_tmp                      stats32_finish_kernel
+//   5     class 1 without skewness / kurtosis            the same, without the third and fourth moments    stats32_finish_kernel
+//   2     "full": flux / spectrum bands / sub-bands /    MFCC, raw sums, bins 0..768 in a.mag_out,         stats32_finish_kernel,
+//         amplitude wanted, nobody reads above bin 768   spectrum bands 26 / 27                            bands_kernel, hop_kernel
+//   3     full with kFramesWholeSpectrum                 the same with bins 0..1023 stored                 + the whitening kernels
+//   4     "magnitude": kFramesStatsLater (bands_kernel   MFCC, bins 0..1023 in a.mag_out, spectrum bands   bands_kernel (takes the
+//         runs anyway and takes the statistics)          26 / 27, amplitude peak / rms of the hop          statistics too)
+//   6     class 4 for large batches that nobody reads    the same with bins 0..768 stored                  bands_kernel
+//         above bin 768 (launch_frames32)
+//
+// Statistics classes (1, 5) and full classes (2, 3) keep sums over the analysis range (bins 1..738) next to the FFT
+// registers; the statistics of the full classes cost this kernel 250-300 bytes of scratch per lane and more than half of
+// its time.  FEAT 5 -- the descriptor set BASELINE.json's north star names (MFCC + rms, centroid, spread, rolloff,
+// flatness) -- keeps four registers and two operations per magnitude less.
+// Full classes (2, 3): the statistics class that also leaves the magnitudes in a.mag_out for bands_kernel and the whitening
+// kernels and the two spectrum bands above the analysis range (bins 738..904, 905..1023: sums of |X|^2 straight from the
+// mirrored halves of rows 0..8, no square root).  FEAT 2 stores what the statistics class computes anyway: bins 0..768,
+// all bands_kernel reads.  FEAT 3 also produces and stores the mirrored blocks of rows 0..7 (bins 769..1023): the whole
+// spectrum, for the whitening follower / fail-safe f0 and the magnitude output.
+// Magnitude classes (4, 6): the MFCC class that also leaves the magnitude spectrum in a.mag_out -- every row untangled in
+// pairs, bins 0..511 from the direct halves, 513..1023 from the mirrored ones, flushed like the reference's -- plus the two
+// spectrum bands above bin 737 and the amplitude of the hop (SA:1760-1783).  They keep no sums across rows: the spectral
+// statistics are bands_kernel's (seven sums more in a kernel that has the rows in its registers anyway).  FEAT 6 (round 6):
+// the mirrored blocks of rows 0..7 (bins 769..1023) are not stored and their square roots not taken (spectrum bands 26 / 27
+// are sums of |X|^2): 6 KiB of stores per frame instead of 8 in a kernel that runs at the memory system's rate.
+//
+// LO_LDS: the overlap half of a frame (rows 0..15 = the hop of the frame before) either stays in 32 registers from frame to
+// frame (classes 0, 1, 5: they have them) or comes back from the cache by a second LDS-DMA into the upper half of the wave's
+// plane, asked for at the bottom of the loop with the window pairs: the classes that keep sums or stored rows next to the
+// FFT registers spilled those 32 registers (128 B of scratch per lane and frame pair, written and read back: 4 KiB per
+// frame each way -- which the counters showed as HBM traffic, the scratch lines do not survive in L2 next to the streaming
+// stores).  (Measured: magnitude class 2.35 -> 1.99 ms on the C4 share, full classes 23.1 -> 20.7 ms on 5.12 M frames; the
+// statistics class, which spilled 44 bytes, 16.1 -> 17.7 ms and the MFCC class 493 -> 422 M frames/s: they keep the
+// registers.)
+// HOP_NT: cache policy of the classes that fetch every hop twice (round 5, A/B on the C4 share,
+// profiles/r05/ab_cache_policy.txt): the first read without the non-temporal hint -- the line is asked for again one frame
+// later -- and the magnitude stores with it (8 KiB per frame streaming through L2 would push those lines out): 2.14 ->
+// 2.02 ms.  The second read, as the next frame's overlap half, is always non-temporal.
+template <int FEAT>
+struct Class32 {
+  static constexpr bool MAGS = (FEAT == 4 || FEAT == 6);                  // magnitude classes
+  static constexpr bool MAGS_UPPER = (FEAT == 4);                         // .. that store bins 769..1023 too
+  static constexpr bool LO_LDS = (FEAT >= 2 && FEAT <= 4) || FEAT == 6;   // overlap half re-fetched into the upper plane
+  static constexpr bool HOP_NT = !LO_LDS;                                 // first read of a hop: non-temporal
+  static constexpr bool STATS = (FEAT >= 1 && FEAT <= 3) || FEAT == 5;    // sums over the analysis range, rows untangled in pairs
+  static constexpr bool MOMENTS34 = (FEAT != 5);                          // .. with the third and fourth moments
+  static constexpr bool STORE = (FEAT == 2 || FEAT == 3);                 // full classes: bins 0..768 into a.mag_out
+  static constexpr bool UPPER = (FEAT == 3);                              // .. and bins 769..1023
+  // rows of 32 bins that are untangled directly: bins 0..383 for the mel filters, 0..511 (+ their mirrored blocks) for
+  // the spectral statistics
+  static constexpr int MR = (FEAT >= 1) ? 16 : kMel32Rows;
+};
+constexpr int kMelEarly = 4;   // magnitude classes: group of the untangle behind which the mel weights are asked for
+
+// ---- what a wave works out once and keeps for the whole kernel (lane = 32 h + q); the kernel's prologue fills it in and
+// explains each member ----
+struct Wave32 {
+  int lane, h, q;
+  __amdgpu_buffer_rsrc_t win_rs, mel_rs;
+  int q16;
+  const double2 *tw, *post;
+  const double *dct, *logc;
+  double* pw;
+  lds_vdouble2* pr;
+  int partner, dh;
+  unsigned char* plane_bytes;
+  unsigned plane_lds;
+  double k_tiny, k_three;
+  unsigned long long k_lane0;
+  lds_vdouble* hop;
+};
+
+// ---- E: real parts, then imaginary parts through the same plane (a wave's DS operations execute in order, so the
+// second round of writes needs no wait for the first round of reads); `queue_behind` issues what is to queue up behind
+// them (the first two groups of twiddles) ----
+template <class F>
+__device__ __forceinline__ void exchange32(cx<double> (&v)[32], double* pw, lds_vdouble2* pr, F queue_behind) {
+  double re[32], im[32];
+#pragma unroll
+  for (int k1 = 0; k1 < 32; ++k1) pw[kRowSlots * k1] = v[k1].re;
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    const f64x2_t two = pr[m];
+    re[2 * m] = two.x;
+    re[2 * m + 1] = two.y;
+  }
+#pragma unroll
+  for (int k1 = 0; k1 < 32; ++k1) pw[kRowSlots * k1] = v[k1].im;
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    const f64x2_t two = pr[m];
+    im[2 * m] = two.x;
+    im[2 * m + 1] = two.y;
+  }
+  queue_behind();
+#pragma unroll
+  for (int n2 = 0; n2 < 32; ++n2) v[n2] = {re[n2], im[n2]};
+}
+
+// ---- T + first radix-4 stage of P2: the factors w1024^(n2 k1) are fused into the first stage of the 32-point DFT.
+// Twiddles by first-stage butterfly: group g = butterflies j = 2 g, 2 g + 1 on rows j, j + 8, j + 16, j + 24 ----
+__device__ void load_tw(double2 (&t)[32], const double2* tw, int g) {
+#pragma unroll
+  for (int j = 2 * g; j < 2 * g + 2; ++j)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (j + 8 * i != 0) t[j + 8 * i] = tw[32 * (j + 8 * i)];
+}
+__device__ void bfly_tw(cx<double> (&v)[32], const double2 (&t)[32], int g) {
+#pragma unroll
+  for (int j = 2 * g; j < 2 * g + 2; ++j) {
+    const cx<double> w1{t[j + 8].x, t[j + 8].y}, w2{t[j + 16].x, t[j + 16].y}, w3{t[j + 24].x, t[j + 24].y};
+    if (j == 0) f32x32::radix4_tw3(v[0], v[8], v[16], v[24], w1, w2, w3);
+    else f32x32::radix4_tw4(v[j], v[j + 8], v[j + 16], v[j + 24], cx<double>{t[j].x, t[j].y}, w1, w2, w3);
+  }
+}
+// two butterflies at a time, the twiddles of the butterflies after next in flight (groups 0, 1 came behind the exchange)
+__device__ void twiddled_first_stage(cx<double> (&v)[32], double2 (&t)[32], const double2* tw) {
+  bfly_tw(v, t, 0);
+  load_tw(t, tw, 2);
+  __builtin_amdgcn_sched_barrier(0);
+  bfly_tw(v, t, 1);
+  load_tw(t, tw, 3);
+  __builtin_amdgcn_sched_barrier(0);
+  bfly_tw(v, t, 2);
+  bfly_tw(v, t, 3);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// ---- statistics classes: per-lane partial sums over this lane's bins of the analysis range (bins 1..738, j = bin - 1):
+// sum m, m^2, j m, j^2 m, m^3, m^4 and the product of (m + 1e-20) in two halves (24 factors would underflow) ----
+template <bool MOMENTS34>
+struct Sums32 {
+  const Wave32& wv;
+  double s1 = 0.0, s2 = 0.0, sj = 0.0, sjj = 0.0, s3 = 0.0, s4 = 0.0, prod_a = 1.0, prod_b = 1.0;
+  double jq = 0.0;     // j of this lane's bin in the next direct row
+  double jmir = 0.0;   // j of this lane's bin in the next mirrored block: 1023 - q - 32 r, r = 8, 9, ..
+  // One value's contribution: the direct rows 0..15 (row 0 without bin 0; rows 0..11 after the mel stage, when the
+  // registers of the FFT are free, rows 12..15 as they are produced), bin 512, and the mirrored blocks M_15..M_8 (of
+  // M_8 = bins 737..768 only two bins).  Magnitudes below sqrt(DBL_MIN) are 0 in the reference (TAudioMath::Magnitude
+  // runs with DAZ + FZ): a silent frame has centroid 0, not (n - 1) / 2.
+  // in_range: this lane's bin lies inside the sums; all_in_range: so does every lane's.  store_at: full classes, where the
+  // flushed value goes (nullptr: nowhere) -- a bin outside the sums is not outside the spectrum.  prod: prod_a or prod_b.
+  __device__ void add(double value, double j, bool in_range, bool all_in_range, double* store_at, double& prod) {
+    const bool audible = value > wv.logc[kCSqrtMin];
+    const bool ok = in_range && audible;
+    const double m = ok ? value : 0.0;
+    if (store_at) *store_at = all_in_range ? m : (audible ? value : 0.0);
+    const double m2 = m * m;
+    const double jm = j * m;
+    s1 += m;
+    s2 += m2;
+    sj += jm;
+    sjj = fma(j, jm, sjj);
+    if (MOMENTS34) {
+      s3 = fma(m2, m, s3);
+      s4 = fma(m2, m2, s4);
+    }
+    prod *= ok ? (value + wv.logc[kCEps]) : 1.0;
+  }
+  // direct row r (bins 32 r + q; bin 0 is outside the sums)
+  __device__ void add_row(int r, const double* mag, double* store_at) {
+    add(mag[r], jq, (r == 0) ? (wv.q != 0) : true, r != 0, store_at, (r < 12) ? prod_a : prod_b);
+    jq += wv.logc[kC32];
+  }
+};
+
+// ---- U: the untangle of one frame behind P2 -- partner fetch, one row, the stores of the full and magnitude classes,
+// the MFCC class' schedule.  A closure over the kernel's registers: the arrays and the values the kernel goes on using
+// stay the kernel's own and are held by reference, as the lambdas this replaces held them (by-value copies and owned
+// members moved the device code of classes 2, 3, 4 and 6). ----
+template <int FEAT>
+struct Spectrum32 {
+  using C = Class32<FEAT>;
+  const Wave32& wv;
+  const FrameArgs& a;
+  const Chunk& ch;
+  const int& fi;
+  const int& nfr;
+  cx<double> (&v)[32];               // v[k2] = Z[q + 32 k2]
+  double (&mag)[C::MR];              // mag[r] = |X[q + 32 r]|
+  cx<double> (&pp)[C::MR];           // partner values and post-twiddles in flight
+  double2 (&pw2)[C::MR];
+  double (&mwt)[2 * kMel32Loads];    // packed mel weights
+  double (&mir)[4];                  // pairs: M_12..M_15 (index r - 12)
+  double& band26;                    // full and magnitude classes: sums of |X|^2 over bins 738..904 and 905..1023
+  double& band27;                    // (spectrum bands 26, 27)
+  // statistics classes: magnitudes of rows 0..11 wait here for the rolloff walk (upper part of the wave's exchange
+  // plane: 384 doubles per half behind the 8 KiB the hop DMA writes)
+  double* const& park;
+  Sums32<C::MOMENTS34> sums{wv};
+  // magnitude classes: the two pointers of this half's row (+ 32 r: bin 32 r + q; - 32 r: bin 1024 - 32 r - q), rebuilt
+  // before every group of rows
+  double* rowd = nullptr;
+  double* rowm = nullptr;
+  lds_bytes* stage_w = nullptr;      // MFCC class: this lane's column of the partner staging area, written and read
+  lds_bytes* stage_r = nullptr;
+
+  __device__ void load_mel() {
+#pragma unroll
+    for (int i = 0; i < kMel32Loads; ++i) {
+      const double2 two = table_load2(wv.mel_rs, wv.q16, 512 * i);
+      mwt[2 * i] = two.x;
+      mwt[2 * i + 1] = two.y;
+    }
+  }
+  // full classes: this half's row of a.mag_out; a frame past the end of the half's chunk writes the spare row behind
+  // the last frame instead (no branch around the stores).  Stored magnitudes are flushed like the reference's
+  // (TAudioMath::Magnitude runs with DAZ + FZ): exactly 0 at or below kFlushLevel -- the value the sums take anyway.
+  // The address is rebuilt at every group of stores: two pointers kept for the whole frame are four registers
+  // this kernel does not have.
+  __device__ double* mag_row() {
+    int fl = fi, ql = wv.lane;
+    asm volatile("" : "+v"(ql), "+s"(fl));
+    const int64_t mrow = (fl < nfr) ? (int64_t)ch.frame0 + fl : a.mag_spare_row;
+    return a.mag_out + mrow * 1024 + (ql & 31);          // + 32 r: bin 32 r + q;  + 1024 - 2 q - 32 r: bin 1024 - 32 r - q
+  }
+  __device__ void mag_rows() {
+    rowd = mag_row();
+    int ql = wv.lane;
+    asm volatile("" : "+v"(ql));
+    rowm = rowd + 1024 - 2 * (ql & 31);
+  }
+  // the store that flushes like TAudioMath::Magnitude under DAZ + FZ
+  __device__ void store_mag(double* p, double value) { __builtin_nontemporal_store(value > wv.logc[kCSqrtMin] ? value : 0.0, p); }
+
+  // MFCC class: the partner rows come through the wave's plane.  The thirteen registers S(0) = v[0], S(s) = v[32 - s]
+  // hold every partner: row r pairs lane q != 0 with S(r + 1) of lane 32 - q and lane 0 with its own S(r).  Every lane
+  // stores S(s) as one 16-byte {re, im} at [half][slot s - 4 b][q] of the staging area behind the logarithm broadcast
+  // (512 bytes a slot, kPartnerSlots slots a half), and reads row r at its own base + 512 (r - 4 b): the base is slot 1,
+  // column 32 - q for q != 0 and slot 0, column 0 for q == 0 -- lanes 0 and 32 read back what they wrote one value
+  // earlier, so no lane is special and there is no EXEC rewrite.  Batch b = rows 4 b .. 4 b + 3 stages S(4 b) .. S(4 b + 4)
+  // in slots 0..4; a wave's DS operations execute in order, so the writes of a batch queue up behind the reads of the
+  // batch before with no wait.  ds_write_b128 is served 8 contiguous lanes (128 contiguous bytes) at a time; the 16-lane
+  // groups of ds_read_b128 meet the 16-byte columns (32 - q) mod 16 and lane 0's column 0 of another slot: 16 different
+  // ones (tools/fft32_dataflow_model.py).
+  __device__ void begin() {
+    if (C::STATS) {
+      int ql = wv.lane;
+      asm volatile("" : "+v"(ql));
+      sums.jq = (double)((ql & 31) - 1);
+      sums.jmir = (double)(767 - (ql & 31));   // M_8: bin 1024 - 256 - q
+    }
+    if constexpr (FEAT == 0) {
+      int ln = wv.lane;
+      asm volatile("" : "+v"(ln));
+      const int hq = ln & 31;
+      lds_bytes* const half_stage = (lds_bytes*)wv.plane_bytes + kPartnerStage + kPartnerSlots * 512 * (ln >> 5);
+      stage_w = half_stage + 16 * hq;
+      stage_r = half_stage + (hq ? 1024 - 16 * hq : 0);
+    }
+  }
+  __device__ void stage(int b) {
+#pragma unroll
+    for (int j = 0; j < kPartnerSlots; ++j) {
+      const cx<double> s = v[(32 - (4 * b + j)) & 31];
+      *(lds_vdouble2*)(stage_w + 512 * j) = f64x2_t{s.re, s.im};
+    }
+  }
+  // partner Z[1024 - k] of row r (MFCC class: a 16-byte read of the partner image; the others: cross-lane) and its
+  // post-twiddle (LDS), asked for one step ahead of row(r)
+  __device__ void fetch(int r) {
+    if constexpr (FEAT == 0) {
+      const f64x2_t two = *(lds_vdouble2*)(stage_r + 512 * (r & 3));
+      pp[r] = {two.x, two.y};
+    } else {
+      pp[r] = {__shfl(v[31 - r].re, wv.partner), __shfl(v[31 - r].im, wv.partner)};
+    }
+    pw2[r] = wv.post[32 * (r % kMel32Rows)];
+  }
+  // Untangle + magnitude of row r.  Statistics and magnitude classes untangle the bins in PAIRS.  X[k] and X[1024 - k]
+  // come from the same (Z[k], Z[1024 - k]): X[k] = E + w O, |X[1024 - k]| = |E - w O|, so row r (bins 32 r + q) also yields
+  // the "mirrored block" M_r = bins 32 (31 - r) + 1 .. 32 (32 - r) -- in reversed lane order (lane q holds bin
+  // 1024 - 32 r - q; lane 0 the block's last bin) -- for ten more operations instead of a second fetch + untangle.  Rows
+  // 0..15, bin 512 (lane 0 of row 16, its own partner) and M_15..M_8 cover the analysis range 1..738: 16 untangle steps
+  // instead of 24.
+  __device__ void row(int r) {
+    cx<double> p = pp[r];
+    // q == 0: bin 32 r pairs with this lane's Z[1024 - 32 r] (MFCC class: the plane has delivered it)
+    if constexpr (FEAT != 0) keep_lane0(p.re, p.im, v[(32 - r) & 31].re, v[(32 - r) & 31].im, wv.k_lane0);
+    const cx<double> z = v[r];
+    double2 wq = pw2[r];
+    if (r >= kMel32Rows) {   // w2048^(q + 32 r) = w2048^(q + 32 (r - 12)) w2048^384
+      const double cr = wv.logc[kCRotRe], ci = wv.logc[kCRotIm];
+      wq = double2{fma(wq.x, cr, -wq.y * ci), fma(wq.x, ci, wq.y * cr)};
+    }
+    const double er = z.re + p.re, ei = z.im - p.im;   // E = Z + conj(P)
+    const double orr = z.im + p.im, oi = p.re - z.re;  // O = -i (Z - conj(P))
+    if (C::MAGS) {
+      const double tr = fma(wq.x, orr, -wq.y * oi), ti = fma(wq.x, oi, wq.y * orr);   // w O
+      const double xr = er + tr, xi = ei + ti, yr = er - tr, yi = ei - ti;
+      const double md = mag_sqrt_mel(xr, xi, wv.k_tiny, wv.k_three);                  // |X[32 r + q]|
+      const double mv = mag_sqrt_mel(yr, yi, wv.k_tiny, wv.k_three);                  // |X[1024 - 32 r - q]|
+      if (r < kMel32Rows) park[32 * r + wv.q] = md;    // rows 0..11 wait in LDS for the mel stage (no register to spare here)
+      store_mag(rowd + 32 * r, md);
+      if (C::MAGS_UPPER || r >= 8) {                                                   // bins 1024 - 32 r - q: above 768 for r < 8
+        if (!(r == 0 && wv.q == 0)) store_mag(rowm - 32 * r, mv);                        // (row 0, lane 0 would be bin 1024)
+      }
+      // spectrum bands 26 = bins 738..904 and 27 = bins 905..1023 lie in the mirrored halves of rows 0..8
+      if (r <= 8) {
+        const double sq = fma(yi, yi, yr * yr);
+        if (r < 3) band27 += (r == 0 && wv.q == 0) ? 0.0 : sq;
+        else if (r == 3) { band27 += (wv.q <= 23) ? sq : 0.0; band26 += (wv.q <= 23) ? 0.0 : sq; }
+        else if (r < 8) band26 += sq;
+        else band26 += (wv.q <= 30) ? sq : 0.0;                                          // M_8 = bins 737..768
+      }
+    } else if (C::STATS && (C::STORE || r >= 8)) {
+      const double tr = fma(wq.x, orr, -wq.y * oi), ti = fma(wq.x, oi, wq.y * orr);   // w O
+      const double xr = er + tr, xi = ei + ti, yr = er - tr, yi = ei - ti;
+      mag[r] = mag_sqrt_mel(xr, xi, wv.k_tiny, wv.k_three);
+      if (r < 8) {
+        // the mirrored block lies above the analysis range (bins 769..1023): |X|^2 into the two spectrum bands there
+        // (M_3 = bins 897..928 holds the edge at 905); row 0, lane 0 would be bin 1024, which does not exist
+        const double sq = fma(yi, yi, yr * yr);
+        if (r < 3) band27 += (r == 0 && wv.q == 0) ? 0.0 : sq;
+        else if (r == 3) { band27 += (wv.q <= 23) ? sq : 0.0; band26 += (wv.q <= 23) ? 0.0 : sq; }
+        else band26 += sq;
+        if (C::UPPER) {
+          const double mv = mag_sqrt_mel(yr, yi, wv.k_tiny, wv.k_three);
+          double* const dst = mag_row() + (1024 - 32 * r) - 2 * wv.q;
+          if (!(r == 0 && wv.q == 0)) *dst = mv > wv.logc[kCSqrtMin] ? mv : 0.0;
+        }
+      } else {
+        const double mv = mag_sqrt_mel(yr, yi, wv.k_tiny, wv.k_three);                // |X[1024 - k]|
+        if (r < kMel32Rows) park[32 * (r + 4) + wv.q] = mv;    // M_8..M_11 wait in LDS (slots 12..15) for the registers of the FFT
+        else {
+          mir[r - kMel32Rows] = mv;
+          sums.add(mv, sums.jmir, true, true, C::STORE ? mag_row() + (1024 - 32 * r) - 2 * wv.q : nullptr, sums.prod_b);
+          sums.jmir -= wv.logc[kC32];
+        }
+      }
+    } else {
+      const double xr = fma(wq.x, orr, fma(-wq.y, oi, er));
+      const double xi = fma(wq.x, oi, fma(wq.y, orr, ei));
+      mag[r] = mag_sqrt_mel(xr, xi, wv.k_tiny, wv.k_three);
+    }
+    if (C::STATS && r >= kMel32Rows) sums.add_row(r, mag, C::STORE ? mag_row() + 32 * r : nullptr);
+  }
+
+  // U, MFCC class: four rows at a time, the next four rows' partner values and post-twiddles in flight; every batch of
+  // four rows stages its five partner registers in the plane first
+  __device__ void untangle_mfcc() {
+    stage(0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) fetch(r);
+    __builtin_amdgcn_sched_barrier(0);
+    stage(1);
+#pragma unroll
+    for (int r = 4; r < 8; ++r) fetch(r);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) row(r);
+    __builtin_amdgcn_sched_barrier(0);
+    stage(2);
+#pragma unroll
+    for (int r = 8; r < 12; ++r) fetch(r);
+#pragma unroll
+    for (int r = 4; r < 8; ++r) row(r);
+    __builtin_amdgcn_sched_barrier(0);
+    // the packed mel rows come from global memory (L1/L2-resident): issued here, when two thirds of the FFT
+    // registers are dead
+    load_mel();
+#pragma unroll
+    for (int r = 8; r < 12; ++r) row(r);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+};
 
 template <int FEAT, bool SCALED>
 __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs a) {
-  // FEAT 4 ("magnitude" class, for the same masks when bands_kernel runs anyway: flux, spectrum bands or sub-band
-  // descriptors are wanted): the MFCC class that also leaves the whole magnitude spectrum in a.mag_out -- every row
-  // untangled in pairs, bins 0..511 from the direct halves, 513..1023 from the mirrored ones, flushed like the
-  // reference's -- plus the two spectrum bands above bin 737.  It keeps no sums across rows: the spectral statistics
-  // are bands_kernel's (seven sums more in a kernel that has the rows in its registers anyway), the amplitude of the
-  // hop hop_kernel's.  The statistics of the full classes cost this kernel 250-300 bytes of scratch per lane and more
-  // than half of its time.
-  // FEAT 6 (round 6): the magnitude class for masks whose later kernels read bins 0..767 only (bands_kernel; no whitening
-  // follower, no magnitude output: !kFramesWholeSpectrum) -- the mirrored blocks of rows 0..7 (bins 769..1023) are not
-  // stored and their square roots not taken (spectrum bands 26 / 27 are sums of |X|^2): 6 KiB of stores per frame instead
-  // of 8 in a kernel that runs at the memory system's rate.
-  constexpr bool MAGS = (FEAT == 4 || FEAT == 6);
-  constexpr bool MAGS_UPPER = (FEAT == 4);
-  // The overlap half of a frame (rows 0..15 = the hop of the frame before) either stays in 32 registers from frame to
-  // frame (MFCC class: it has them) or comes back from the cache by a second LDS-DMA into the upper half of the wave's
-  // plane, asked for at the bottom of the loop with the window pairs: the classes that keep sums or stored rows next to
-  // the FFT registers spilled those 32 registers (128 B of scratch per lane and frame pair, written and read back: 4 KiB
-  // per frame each way -- which the counters showed as HBM traffic, the scratch lines do not survive in L2 next to the
-  // streaming stores).
-  constexpr int kMelEarly = 4;   // magnitude class: group of the untangle behind which the mel weights are asked for
-  // (measured: magnitude class 2.35 -> 1.99 ms on the C4 share, full classes 23.1 -> 20.7 ms on 5.12 M frames; the
-  // statistics class, which spilled 44 bytes, 16.1 -> 17.7 ms and the MFCC class 493 -> 422 M frames/s: they keep the
-  // registers)
-  constexpr bool LO_LDS = (FEAT >= 2 && FEAT <= 4) || FEAT == 6;
-  // Cache policy of the classes that fetch every hop twice (round 5, A/B on the C4 share, profiles/r05/ab_cache_policy.txt):
-  // the first read without the non-temporal hint -- the line is asked for again one frame later -- and the magnitude
-  // stores with it (8 KiB per frame streaming through L2 would push those lines out): 2.14 -> 2.02 ms.
-  constexpr bool kHopNt = !LO_LDS;   // first read of a hop
-  constexpr bool kLoNt = true;       // its second read, as the next frame's overlap half
-  // FEAT 5: the statistics class for masks without skewness / kurtosis -- the descriptor set BASELINE.json's north star
-  // names (MFCC + rms, centroid, spread, rolloff, flatness) -- keeps no third and fourth moments: four registers and two
-  // operations per magnitude less.
-  constexpr bool STATS = (FEAT >= 1 && FEAT <= 3) || FEAT == 5;
-  constexpr bool MOMENTS34 = (FEAT != 5);
-  constexpr bool PAIRS = STATS;
-  // FEAT 2, 3 ("full" classes, for masks with flux / spectrum bands / sub-band descriptors / amplitude): the statistics
-  // class that also leaves the magnitudes in a.mag_out for bands_kernel and the whitening kernels, the amplitude peak /
-  // rms of the hop (SA:1760-1783) and the two spectrum bands above the analysis range (bins 738..904, 905..1023: sums
-  // of |X|^2 straight from the mirrored halves of rows 0..8, no square root).  FEAT 2 stores what the statistics class
-  // computes anyway: bins 0..768, all bands_kernel reads.  FEAT 3 also produces and stores the mirrored blocks of rows
-  // 0..7 (bins 769..1023): the whole spectrum, for the whitening follower / fail-safe f0 and the magnitude output.
-  constexpr bool STORE = (FEAT == 2 || FEAT == 3);
-  constexpr bool UPPER = (FEAT == 3);
-  // rows of 32 bins that are untangled directly: bins 0..383 for the mel filters, 0..511 (+ their mirrored blocks) for
-  // the spectral statistics
-  constexpr int MR = (FEAT >= 1) ? 16 : kMel32Rows;
-  using Map = Lds32<kMel32Rows>;   // untangle factors of rows 0..11; rows 12..15 are rows 0..3 times w2048^384
+  using C = Class32<FEAT>;
+  constexpr bool MAGS = C::MAGS, LO_LDS = C::LO_LDS, kHopNt = C::HOP_NT, STATS = C::STATS, STORE = C::STORE;
+  constexpr int MR = C::MR;
+  using Map = Lds32;
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform: SGPR arithmetic
@@ -367,6 +688,7 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
   asm volatile("" : "+s"(k_tiny), "+s"(k_three), "+s"(k_lane0));
   lds_vdouble* const hop = (lds_vdouble*)(plane_bytes + 256 * h + 8 * q);   // + 64 r (8-byte units: 512 bytes a row)
 
+  const Wave32 wv{lane, h, q, win_rs, mel_rs, q16, tw, post, dct, logc, pw, pr, partner, dh, plane_bytes, plane_lds, k_tiny, k_three, k_lane0, hop};
   const float* const pcm = reinterpret_cast<const float*>(a.pcm);
 
   // Work queue.  A static split is badly unbalanced here: of the two waves that share a SIMD the older one wins
@@ -403,7 +725,7 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
 #pragma unroll
       for (int r = 0; r < 16; ++r) lo[r] = src8[32 * r];
     } else {
-      dma_hop<kLoNt>(dsrc - kHop, plane_lds + 8192);   // rows 0..15 of frame 0
+      dma_hop<true>(dsrc - kHop, plane_lds + 8192);   // rows 0..15 of frame 0
     }
     // frame 0's new hop (every DS operation of the previous chunk has been waited for)
     dma_hop<kHopNt>(dsrc, plane_lds);
@@ -526,44 +848,7 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
       // of twiddles queue up behind them ----
       // twiddles by first-stage butterfly: group g = butterflies j = 2 g, 2 g + 1 on rows j, j + 8, j + 16, j + 24
       double2 t[32];
-      auto load_tw = [&](int g) {
-#pragma unroll
-        for (int j = 2 * g; j < 2 * g + 2; ++j)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if (j + 8 * i != 0) t[j + 8 * i] = tw[32 * (j + 8 * i)];
-      };
-      auto bfly_tw = [&](int g) {
-#pragma unroll
-        for (int j = 2 * g; j < 2 * g + 2; ++j) {
-          const cx<double> w1{t[j + 8].x, t[j + 8].y}, w2{t[j + 16].x, t[j + 16].y}, w3{t[j + 24].x, t[j + 24].y};
-          if (j == 0) f32x32::radix4_tw3(v[0], v[8], v[16], v[24], w1, w2, w3);
-          else f32x32::radix4_tw4(v[j], v[j + 8], v[j + 16], v[j + 24], cx<double>{t[j].x, t[j].y}, w1, w2, w3);
-        }
-      };
-      {
-        double re[32], im[32];
-#pragma unroll
-        for (int k1 = 0; k1 < 32; ++k1) pw[kRowSlots * k1] = v[k1].re;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-          const f64x2_t two = pr[m];
-          re[2 * m] = two.x;
-          re[2 * m + 1] = two.y;
-        }
-#pragma unroll
-        for (int k1 = 0; k1 < 32; ++k1) pw[kRowSlots * k1] = v[k1].im;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-          const f64x2_t two = pr[m];
-          im[2 * m] = two.x;
-          im[2 * m + 1] = two.y;
-        }
-        load_tw(0);
-        load_tw(1);
-#pragma unroll
-        for (int n2 = 0; n2 < 32; ++n2) v[n2] = {re[n2], im[n2]};
-      }
+      exchange32(v, pw, pr, [&] { load_tw(t, tw, 0); load_tw(t, tw, 1); });
       // ---- the next frame's new hop: LDS-DMA into the plane once the exchange reads have returned (the DMA is a
       // vector-memory operation: nothing else orders it behind this wave's DS reads).  The last frame of a chunk
       // re-reads its own hop (no branch: the loop body stays one basic block).
@@ -574,15 +859,7 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
 
       // ---- T + P2: v[k2] = Z[q + 32 k2]; the factors w1024^(n2 k1) are fused into the first radix-4 stage of
       // the 32-point DFT, two butterflies at a time, the twiddles of the butterflies after next in flight ----
-      bfly_tw(0);
-      load_tw(2);
-      __builtin_amdgcn_sched_barrier(0);
-      bfly_tw(1);
-      load_tw(3);
-      __builtin_amdgcn_sched_barrier(0);
-      bfly_tw(2);
-      bfly_tw(3);
-      __builtin_amdgcn_sched_barrier(0);
+      twiddled_first_stage(v, t, tw);
       AFX_STAMP(4);   // DMA issue + twiddled first stage
       f32x32::dft32_rest(v);
       __builtin_amdgcn_sched_barrier(0);
@@ -594,218 +871,37 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
       cx<double> pp[MR];
       double2 pw2[MR];
       double mwt[2 * kMel32Loads];
-      auto load_mel = [&]() {
-#pragma unroll
-        for (int i = 0; i < kMel32Loads; ++i) {
-          const double2 two = table_load2(mel_rs, q16, 512 * i);
-          mwt[2 * i] = two.x;
-          mwt[2 * i + 1] = two.y;
-        }
-      };
-      // statistics class: per-lane partial sums over this lane's bins of the analysis range (bins 1..738, j = bin - 1):
-      // sum m, m^2, j m, j^2 m, m^3, m^4 and the product of (m + 1e-20) in two halves (24 factors would underflow)
-      double s1 = 0.0, s2 = 0.0, sj = 0.0, sjj = 0.0, s3 = 0.0, s4 = 0.0, prod_a = 1.0, prod_b = 1.0;
-      double jq = 0.0, pa = 0.0;
-      double jmir = 0.0;   // pairs: j of this lane's bin in the next mirrored block: 1023 - q - 32 r, r = 8, 9, ..
-      double mir[4] = {0.0, 0.0, 0.0, 0.0}, cmid = 0.0;   // pairs: M_12..M_15 (index r - 12) and bin 512 (lane 0)
-      // statistics class: magnitudes of rows 0..11 wait here for the rolloff walk (upper part of the wave's exchange
-      // plane: 384 doubles per half behind the 8 KiB the hop DMA writes)
+      double mir[4] = {0.0, 0.0, 0.0, 0.0};
+      double band26 = 0.0, band27 = 0.0;   // full and magnitude classes: sums of |X|^2 over bins 738..904 and 905..1023 (spectrum bands 26, 27)
+      double cmid = 0.0, pa = 0.0;         // pairs: bin 512 (lane 0); row sums of rows 0..11, taken before they are parked
       double* const park = reinterpret_cast<double*>(plane_bytes + 8192 + 4352 * h);
-      // full classes: this half's row of a.mag_out; a frame past the end of the half's chunk writes the spare row behind
-      // the last frame instead (no branch around the stores).  Stored magnitudes are flushed like the reference's
-      // (TAudioMath::Magnitude runs with DAZ + FZ): exactly 0 at or below kFlushLevel -- the value the sums take anyway.
-      // The address is rebuilt at every group of stores: two pointers kept for the whole frame are four registers
-      // this kernel does not have.
-      auto mag_row = [&]() -> double* {
-        int fl = fi, ql = lane;
-        asm volatile("" : "+v"(ql), "+s"(fl));
-        const int64_t mrow = (fl < nfr) ? (int64_t)ch.frame0 + fl : a.mag_spare_row;
-        return a.mag_out + mrow * 1024 + (ql & 31);          // + 32 r: bin 32 r + q;  + 1024 - 2 q - 32 r: bin 1024 - 32 r - q
-      };
-      double band26 = 0.0, band27 = 0.0;   // full classes: sums of |X|^2 over bins 738..904 and 905..1023 (spectrum bands 26, 27)
-      // magnitude class: the two pointers of this half's row (+ 32 r: bin 32 r + q; - 32 r: bin 1024 - 32 r - q), rebuilt
-      // before every group of rows, and the store that flushes like TAudioMath::Magnitude under DAZ + FZ
-      double* rowd = nullptr;
-      double* rowm = nullptr;
-      auto mag_rows = [&]() {
-        rowd = mag_row();
-        int ql = lane;
-        asm volatile("" : "+v"(ql));
-        rowm = rowd + 1024 - 2 * (ql & 31);
-      };
-      auto store_mag = [&](double* p, double value) { __builtin_nontemporal_store(value > logc[kCSqrtMin] ? value : 0.0, p); };
-      if (STATS) {
-        int ql = lane;
-        asm volatile("" : "+v"(ql));
-        jq = (double)((ql & 31) - 1);
-        if (PAIRS) jmir = (double)(767 - (ql & 31));   // M_8: bin 1024 - 256 - q
-      }
-      // statistics class: one value's contribution to the sums over bins 1..738 (j = bin - 1): the direct rows 0..15
-      // (row 0 without bin 0; rows 0..11 after the mel stage, when the registers of the FFT are free, rows 12..15 as
-      // they are produced), bin 512, and the mirrored blocks M_15..M_8 (of M_8 = bins 737..768 only two bins).
-      // Magnitudes below sqrt(DBL_MIN) are 0 in the reference (TAudioMath::Magnitude runs with DAZ + FZ): a silent
-      // frame has centroid 0, not (n - 1) / 2.
-      // accumulate_at: a value that is not one of the direct rows (mirrored block, bin 512)
-      // store_at: full classes, where the flushed value goes (nullptr: nowhere); every in-range caller stores what it sums
-      auto accumulate_at = [&](double value, double j, bool in_range, double* store_at, bool all_in_range) {
-        const bool audible = value > logc[kCSqrtMin];
-        const bool ok = in_range && audible;
-        const double m = ok ? value : 0.0;
-        if (STORE && store_at) *store_at = all_in_range ? m : (audible ? value : 0.0);
-        const double m2 = m * m;
-        const double jm = j * m;
-        s1 += m;
-        s2 += m2;
-        sj += jm;
-        sjj = fma(j, jm, sjj);
-        if (MOMENTS34) {
-          s3 = fma(m2, m, s3);
-          s4 = fma(m2, m2, s4);
-        }
-        prod_b *= ok ? (value + logc[kCEps]) : 1.0;
-      };
-      auto accumulate = [&](int r, double* store_at) {
-        const bool audible = mag[r] > logc[kCSqrtMin];
-        const bool ok = ((r == 0) ? (q != 0) : true) && audible;
-        const double m = ok ? mag[r] : 0.0;
-        if (STORE && store_at) *store_at = (r == 0) ? (audible ? mag[r] : 0.0) : m;   // bin 0 is outside the sums, not outside the spectrum
-        const double m2 = m * m;
-        const double jm = jq * m;
-        s1 += m;
-        s2 += m2;
-        sj += jm;
-        sjj = fma(jq, jm, sjj);
-        if (MOMENTS34) {
-          s3 = fma(m2, m, s3);
-          s4 = fma(m2, m2, s4);
-        }
-        const double f = ok ? (mag[r] + logc[kCEps]) : 1.0;
-        if (r < 12) prod_a *= f; else prod_b *= f;
-        jq += logc[kC32];
-      };
-      // MFCC class: the partner rows come through the wave's plane.  The thirteen registers S(0) = v[0], S(s) = v[32 - s]
-      // hold every partner: row r pairs lane q != 0 with S(r + 1) of lane 32 - q and lane 0 with its own S(r).  Every lane
-      // stores S(s) as one 16-byte {re, im} at [half][slot s - 4 b][q] of the staging area behind the logarithm broadcast
-      // (512 bytes a slot, kPartnerSlots slots a half), and reads row r at its own base + 512 (r - 4 b): the base is slot 1,
-      // column 32 - q for q != 0 and slot 0, column 0 for q == 0 -- lanes 0 and 32 read back what they wrote one value
-      // earlier, so no lane is special and there is no EXEC rewrite.  Batch b = rows 4 b .. 4 b + 3 stages S(4 b) .. S(4 b + 4)
-      // in slots 0..4; a wave's DS operations execute in order, so the writes of a batch queue up behind the reads of the
-      // batch before with no wait.  ds_write_b128 is served 8 contiguous lanes (128 contiguous bytes) at a time; the 16-lane
-      // groups of ds_read_b128 meet the 16-byte columns (32 - q) mod 16 and lane 0's column 0 of another slot: 16 different
-      // ones (tools/fft32_dataflow_model.py).  The addresses are rebuilt from a laundered lane id every trip.
-      lds_bytes* stage_w = nullptr;
-      lds_bytes* stage_r = nullptr;
-      if constexpr (FEAT == 0) {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int hq = ln & 31;
-        lds_bytes* const half_stage = (lds_bytes*)plane_bytes + kPartnerStage + kPartnerSlots * 512 * (ln >> 5);
-        stage_w = half_stage + 16 * hq;
-        stage_r = half_stage + (hq ? 1024 - 16 * hq : 0);
-      }
-      auto stage = [&](int b) {
-#pragma unroll
-        for (int j = 0; j < kPartnerSlots; ++j) {
-          const cx<double> s = v[(32 - (4 * b + j)) & 31];
-          *(lds_vdouble2*)(stage_w + 512 * j) = f64x2_t{s.re, s.im};
-        }
-      };
-      auto fetch = [&](int r) {
-        if constexpr (FEAT == 0) {
-          const f64x2_t two = *(lds_vdouble2*)(stage_r + 512 * (r & 3));
-          pp[r] = {two.x, two.y};
-        } else {
-          pp[r] = {__shfl(v[31 - r].re, partner), __shfl(v[31 - r].im, partner)};
-        }
-        pw2[r] = post[32 * (r % kMel32Rows)];
-      };
-      auto untangle = [&](int r) {
-        cx<double> p = pp[r];
-        // q == 0: bin 32 r pairs with this lane's Z[1024 - 32 r] (MFCC class: the plane has delivered it)
-        if constexpr (FEAT != 0) keep_lane0(p.re, p.im, v[(32 - r) & 31].re, v[(32 - r) & 31].im, k_lane0);
-        const cx<double> z = v[r];
-        double2 wq = pw2[r];
-        if (r >= kMel32Rows) {   // w2048^(q + 32 r) = w2048^(q + 32 (r - 12)) w2048^384
-          const double cr = logc[kCRotRe], ci = logc[kCRotIm];
-          wq = double2{fma(wq.x, cr, -wq.y * ci), fma(wq.x, ci, wq.y * cr)};
-        }
-        const double er = z.re + p.re, ei = z.im - p.im;   // E = Z + conj(P)
-        const double orr = z.im + p.im, oi = p.re - z.re;  // O = -i (Z - conj(P))
-        if (MAGS) {
-          const double tr = fma(wq.x, orr, -wq.y * oi), ti = fma(wq.x, oi, wq.y * orr);   // w O
-          const double xr = er + tr, xi = ei + ti, yr = er - tr, yi = ei - ti;
-          const double md = mag_sqrt_mel(xr, xi, k_tiny, k_three);                        // |X[32 r + q]|
-          const double mv = mag_sqrt_mel(yr, yi, k_tiny, k_three);                        // |X[1024 - 32 r - q]|
-          if (r < kMel32Rows) park[32 * r + q] = md;    // rows 0..11 wait in LDS for the mel stage (no register to spare here)
-          store_mag(rowd + 32 * r, md);
-          if (MAGS_UPPER || r >= 8) {                                                      // bins 1024 - 32 r - q: above 768 for r < 8
-            if (!(r == 0 && q == 0)) store_mag(rowm - 32 * r, mv);                        // (row 0, lane 0 would be bin 1024)
-          }
-          // spectrum bands 26 = bins 738..904 and 27 = bins 905..1023 lie in the mirrored halves of rows 0..8
-          if (r <= 8) {
-            const double sq = fma(yi, yi, yr * yr);
-            if (r < 3) band27 += (r == 0 && q == 0) ? 0.0 : sq;
-            else if (r == 3) { band27 += (q <= 23) ? sq : 0.0; band26 += (q <= 23) ? 0.0 : sq; }
-            else if (r < 8) band26 += sq;
-            else band26 += (q <= 30) ? sq : 0.0;                                          // M_8 = bins 737..768
-          }
-        } else if (PAIRS && (STORE || r >= 8)) {
-          const double tr = fma(wq.x, orr, -wq.y * oi), ti = fma(wq.x, oi, wq.y * orr);   // w O
-          const double xr = er + tr, xi = ei + ti, yr = er - tr, yi = ei - ti;
-          mag[r] = mag_sqrt_mel(xr, xi, k_tiny, k_three);
-          if (r < 8) {
-            // the mirrored block lies above the analysis range (bins 769..1023): |X|^2 into the two spectrum bands there
-            // (M_3 = bins 897..928 holds the edge at 905); row 0, lane 0 would be bin 1024, which does not exist
-            const double sq = fma(yi, yi, yr * yr);
-            if (r < 3) band27 += (r == 0 && q == 0) ? 0.0 : sq;
-            else if (r == 3) { band27 += (q <= 23) ? sq : 0.0; band26 += (q <= 23) ? 0.0 : sq; }
-            else band26 += sq;
-            if (UPPER) {
-              const double mv = mag_sqrt_mel(yr, yi, k_tiny, k_three);
-              double* const dst = mag_row() + (1024 - 32 * r) - 2 * q;
-              if (!(r == 0 && q == 0)) *dst = mv > logc[kCSqrtMin] ? mv : 0.0;
-            }
-          } else {
-            const double mv = mag_sqrt_mel(yr, yi, k_tiny, k_three);                      // |X[1024 - k]|
-            if (r < kMel32Rows) park[32 * (r + 4) + q] = mv;    // M_8..M_11 wait in LDS (slots 12..15) for the registers of the FFT
-            else {
-              mir[r - kMel32Rows] = mv;
-              accumulate_at(mv, jmir, true, STORE ? mag_row() + (1024 - 32 * r) - 2 * q : nullptr, true);
-              jmir -= logc[kC32];
-            }
-          }
-        } else {
-          const double xr = fma(wq.x, orr, fma(-wq.y, oi, er));
-          const double xi = fma(wq.x, oi, fma(wq.y, orr, ei));
-          mag[r] = mag_sqrt_mel(xr, xi, k_tiny, k_three);
-        }
-        if (STATS && r >= kMel32Rows) accumulate(r, STORE ? mag_row() + 32 * r : nullptr);
-      };
+      Spectrum32<FEAT> s{wv, a, ch, fi, nfr, v, mag, pp, pw2, mwt, mir, band26, band27, park};
+      s.begin();
       if constexpr (MAGS) {
         // magnitude class: sixteen rows in pairs of two, one pair of fetches ahead (the paired form keeps more live per
         // row than the other classes' and every value leaves at once: short groups keep the register file below its limit)
-        fetch(0); fetch(1);
+        s.fetch(0); s.fetch(1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
-          if (g < 7) { fetch(2 * g + 2); fetch(2 * g + 3); }
-          mag_rows();
-          untangle(2 * g);
-          untangle(2 * g + 1);
+          if (g < 7) { s.fetch(2 * g + 2); s.fetch(2 * g + 3); }
+          s.mag_rows();
+          s.row(2 * g);
+          s.row(2 * g + 1);
           // The packed mel rows, asked for in the MIDDLE of the untangle: on gfx950 stores count in vmcnt like loads and
           // retire in order, so weights asked for behind the frame's last store (where the last FFT registers die) made the
           // mel stage wait for every store of the frame.  Half-way through, the rows already untangled have freed 16
           // registers per group; the loads then wait only for the stores issued before them, which are long done when
           // the mel stage starts, and the compiler's wait count lets the later stores stay in flight.
           if (g == kMelEarly) {
-            load_mel();
+            s.load_mel();
           }
           __builtin_amdgcn_sched_barrier(0);
         }
         // bin 512 = lane 0 of row 16 is its own partner: E = 2 Re Z, w O = -2i Im Z (the window carries the 1/2)
         const double er = v[16].re + v[16].re, orr = v[16].im + v[16].im;
         const double cm = mag_sqrt_mel(er, orr, k_tiny, k_three);
-        if (q == 0) store_mag(rowd + 512, cm);
+        if (q == 0) s.store_mag(s.rowd + 512, cm);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int r = 0; r < kMel32Rows; ++r) mag[r] = park[32 * r + q];
@@ -814,44 +910,20 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
         // statistics and full classes: rows in groups of two, one group of fetches ahead.  They keep eighteen doubles of sums
         // next to the FFT registers; with four rows in flight (as below) the allocator spilled 88 bytes per lane, with two 36,
         // and the shorter groups cost less than the spills did (285 -> 291 M frames/s on the star set).
-        fetch(0); fetch(1);
+        s.fetch(0); s.fetch(1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int g = 0; g < 6; ++g) {
-          if (g < 5) { fetch(2 * g + 2); fetch(2 * g + 3); }
-          untangle(2 * g);
-          untangle(2 * g + 1);
+          if (g < 5) { s.fetch(2 * g + 2); s.fetch(2 * g + 3); }
+          s.row(2 * g);
+          s.row(2 * g + 1);
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {
-      // (MFCC class: every batch of four rows stages its five partner registers in the plane first)
-      if constexpr (FEAT == 0) stage(0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) fetch(r);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (FEAT == 0) stage(1);
-#pragma unroll
-      for (int r = 4; r < 8; ++r) fetch(r);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) untangle(r);
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (FEAT == 0) stage(2);
-#pragma unroll
-      for (int r = 8; r < 12; ++r) fetch(r);
-#pragma unroll
-      for (int r = 4; r < 8; ++r) untangle(r);
-      __builtin_amdgcn_sched_barrier(0);
-      // the packed mel rows come from global memory (L1/L2-resident): issued here, when two thirds of the FFT
-      // registers are dead
-      if (FEAT == 0) {
-        load_mel();
-      }
-#pragma unroll
-      for (int r = 8; r < 12; ++r) untangle(r);
-      __builtin_amdgcn_sched_barrier(0);
+        s.untangle_mfcc();
       }
       if (STATS) {   // statistics class: behind the last rows (62 registers in flight that it cannot spare earlier)
-        load_mel();
+        s.load_mel();
       }
       AFX_STAMP(6);   // untangle
 
@@ -867,14 +939,14 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
             if (mel32_touches(f, r)) e[f] += mag[r] * mwt[mel32_pair_index(r, f)];
         __builtin_amdgcn_sched_barrier(0);
         AFX_STAMP(7);   // mel rows (waits for the table loads)
-        if (STATS) {
+        if constexpr (STATS) {
           // statistics class: the mel sums are reduced first (their registers are needed), then rows 12..15 and their mirrors
           const double tot1 = half_sum16(e, lane);
           if ((lane & 1) == (fi & 1)) mel_acc = tot1;
           {
-            double* const row0 = STORE ? mag_row() : nullptr;
+            double* const row0 = STORE ? s.mag_row() : nullptr;
 #pragma unroll
-            for (int r = 0; r < kMel32Rows; ++r) accumulate(r, STORE ? row0 + 32 * r : nullptr);
+            for (int r = 0; r < kMel32Rows; ++r) s.sums.add_row(r, mag, STORE ? row0 + 32 * r : nullptr);
           }
           // rows 0..11 are needed once more (rolloff): their row sums now, the values parked in the part of the
           // exchange plane that the hop DMA does not use
@@ -889,28 +961,25 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
           }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int r = 12; r < 16; ++r) fetch(r);
-          if constexpr (PAIRS) {   // the mirrored blocks of rows 8..11, parked by the untangle stage: bins 737..768 (two of them in range) .. 641..672
-            double* const mrow0 = STORE ? mag_row() + 1024 - 2 * q : nullptr;   // bin 1024 - 32 r - q at - 32 r
+          for (int r = 12; r < 16; ++r) s.fetch(r);
+          // the mirrored blocks of rows 8..11, parked by the untangle stage: bins 737..768 (two of them in range) .. 641..672
+          double* const mrow0 = STORE ? s.mag_row() + 1024 - 2 * q : nullptr;   // bin 1024 - 32 r - q at - 32 r
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const double mv = park[32 * (12 + i) + q];
-              // M_8 = bins 737..768: two of them inside the analysis range, the others (q <= 30) in spectrum band 26
-              if (STORE && i == 0) band26 += (q <= 30) ? 0.25 * (mv * mv) : 0.0;   // (the row sums are of the halved spectrum, x 4 below)
-              accumulate_at(mv, jmir, (i == 0) ? (q >= 30) : true, STORE ? mrow0 - 32 * (8 + i) : nullptr, i != 0);
-              jmir -= logc[kC32];
-            }
+          for (int i = 0; i < 4; ++i) {
+            const double mv = park[32 * (12 + i) + q];
+            // M_8 = bins 737..768: two of them inside the analysis range, the others (q <= 30) in spectrum band 26
+            if (STORE && i == 0) band26 += (q <= 30) ? 0.25 * (mv * mv) : 0.0;   // (the row sums are of the halved spectrum, x 4 below)
+            s.sums.add(mv, s.sums.jmir, (i == 0) ? (q >= 30) : true, i != 0, STORE ? mrow0 - 32 * (8 + i) : nullptr, s.sums.prod_b);
+            s.sums.jmir -= logc[kC32];
           }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int r = 12; r < 16; ++r) untangle(r);
+          for (int r = 12; r < 16; ++r) s.row(r);
           __builtin_amdgcn_sched_barrier(0);
-          if constexpr (PAIRS) {
-            // bin 512 = lane 0 of row 16 is its own partner: E = 2 Re Z, w O = -2i Im Z (the window carries the 1/2)
-            const double er = v[16].re + v[16].re, orr = v[16].im + v[16].im;
-            cmid = (q == 0) ? mag_sqrt_mel(er, orr, k_tiny, k_three) : 0.0;
-            accumulate_at(cmid, logc[kC511], q == 0, (STORE && q == 0) ? mag_row() + 512 : nullptr, true);
-          }
+          // bin 512 = lane 0 of row 16 is its own partner: E = 2 Re Z, w O = -2i Im Z (the window carries the 1/2)
+          const double er = v[16].re + v[16].re, orr = v[16].im + v[16].im;
+          cmid = (q == 0) ? mag_sqrt_mel(er, orr, k_tiny, k_three) : 0.0;
+          s.sums.add(cmid, logc[kC511], q == 0, true, (STORE && q == 0) ? s.mag_row() + 512 : nullptr, s.sums.prod_b);
         }
         // the next frame's window pairs, under the reduction and the log / DCT (statistics class: behind its sums,
         // which need the registers)
@@ -918,7 +987,7 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
 #pragma unroll
           for (int r = 0; r < 32; ++r) w[r] = table_load2(win_rs, q16, 512 * r);
           // (the parked rows have been read: the upper half of the plane is free for the next frame's overlap rows)
-          if constexpr (LO_LDS) dma_hop<kLoNt>(dsrc + (size_t)min(fi + 1, last_d) * kHop - kHop, plane_lds + 8192);
+          if constexpr (LO_LDS) dma_hop<true>(dsrc + (size_t)min(fi + 1, last_d) * kHop - kHop, plane_lds + 8192);
         }
         if (FEAT == 0 || MAGS) {
           if (MAGS) {   // the two free slots of the reduction: spectrum bands 26, 27 (x 4: the window carries an extra 1/2)
@@ -936,15 +1005,15 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
           }
         }
         AFX_STAMP(8);   // window issue + reduction
-        if (STATS) {
+        if constexpr (STATS) {
           // ---- spectral statistics (SA:1808-1933): the sums of this half's frame, reduced over its 32 lanes; the
           //      closed forms (sqrt, divisions, exp / log of the flatness) are left to stats32_finish_kernel ----
           int ln = lane;
           asm volatile("" : "+v"(ln));
           const int hq = ln & 31;
           double st[16];
-          st[0] = s1; st[1] = s2; st[2] = sj; st[3] = sjj; st[4] = s3; st[5] = s4;
-          st[6] = log_lds(prod_a, logc) + log_lds(prod_b, logc);
+          st[0] = s.sums.s1; st[1] = s.sums.s2; st[2] = s.sums.sj; st[3] = s.sums.sjj; st[4] = s.sums.s3; st[5] = s.sums.s4;
+          st[6] = log_lds(s.sums.prod_a, logc) + log_lds(s.sums.prod_b, logc);
           st[7] = STORE ? 4.0 * band26 : 0.0;   // the window carries an extra 1/2 (mag_sqrt_mel): |X|^2 = 4 |X / 2|^2
           st[8] = STORE ? 4.0 * band27 : 0.0;
 #pragma unroll
@@ -966,16 +1035,14 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
           // block sums (rows 0..11: pa, taken before they were parked in LDS); the blocks behind
           // row 11 in bin order are rows 12..15, bin 512, M_15..M_12 (registers), M_11..M_8 (parked): 13 slots
           double rb[16];
-          if constexpr (PAIRS) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) rb[r] = mag[12 + r];
-            rb[4] = cmid;
+          for (int r = 0; r < 4; ++r) rb[r] = mag[12 + r];
+          rb[4] = cmid;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rb[5 + i] = mir[3 - i];
+          for (int i = 0; i < 4; ++i) rb[5 + i] = mir[3 - i];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) rb[9 + i] = (i == 3 && hq < 30) ? 0.0 : park[32 * (15 - i) + hq];
-            rb[13] = rb[14] = rb[15] = 0.0;
-          }
+          for (int i = 0; i < 4; ++i) rb[9 + i] = (i == 3 && hq < 30) ? 0.0 : park[32 * (15 - i) + hq];
+          rb[13] = rb[14] = rb[15] = 0.0;
           double pb = half_sum16(rb, ln);            // lane L: slot (L & 31) >> 1
           // inclusive prefix over the row slots of a half (both lanes of a slot hold the same value)
           // (DPP row shifts, then the last lane of a half's first row into its second row: no LDS round trips)
@@ -1002,28 +1069,23 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
                                                  __builtin_amdgcn_ds_bpermute(idx_a, __double2loint(pb)));
           const double before = (rstar == 0) ? 0.0 : ((prev < 12) ? base_a : base_b);
           // the crossing row's magnitudes, summed along the lanes: rows 0..11 from their LDS parking place
-          double xs;
-          bool okq;
-          int bins_before;
-          if constexpr (PAIRS) {
-            // block rstar in bin order: 0..15 rows, 16 bin 512, 17..20 M_15..M_12 (registers), 21..24 M_11..M_8 (parked);
-            // a mirrored block holds its bins in reversed lane order
-            const bool parked_m = rstar >= 21;
-            const int prow = (rstar < 12) ? rstar : (parked_m ? 36 - rstar : 0);
-            xs = park[32 * prow + (parked_m ? 31 - hq : hq)];
+          // block rstar in bin order: 0..15 rows, 16 bin 512, 17..20 M_15..M_12 (registers), 21..24 M_11..M_8 (parked);
+          // a mirrored block holds its bins in reversed lane order
+          const bool parked_m = rstar >= 21;
+          const int prow = (rstar < 12) ? rstar : (parked_m ? 36 - rstar : 0);
+          double xs = park[32 * prow + (parked_m ? 31 - hq : hq)];
 #pragma unroll
-            for (int r = 12; r < 16; ++r) xs = (rstar == r) ? mag[r] : xs;
-            xs = (rstar == 16) ? cmid : xs;
-            double xm = mir[0];
+          for (int r = 12; r < 16; ++r) xs = (rstar == r) ? mag[r] : xs;
+          xs = (rstar == 16) ? cmid : xs;
+          double xm = mir[0];
 #pragma unroll
-            for (int i = 1; i < 4; ++i) xm = (rstar == 20 - i) ? mir[i] : xm;
-            const int ridx = base_idx + ((31 - hq) << 2);
-            const double xrev = __hiloint2double(__builtin_amdgcn_ds_bpermute(ridx, __double2hiint(xm)),
-                                                 __builtin_amdgcn_ds_bpermute(ridx, __double2loint(xm)));
-            xs = (rstar >= 17 && rstar <= 20) ? xrev : xs;
-            okq = (rstar == 0) ? (hq != 0) : ((rstar == 16) ? (hq == 0) : ((rstar == 24) ? (hq <= 1) : (rstar < 24)));
-            bins_before = (rstar < 16) ? 32 * rstar - (rstar > 0 ? 1 : 0) : ((rstar == 16) ? 511 : 512 + 32 * (rstar - 17));
-          }
+          for (int i = 1; i < 4; ++i) xm = (rstar == 20 - i) ? mir[i] : xm;
+          const int ridx = base_idx + ((31 - hq) << 2);
+          const double xrev = __hiloint2double(__builtin_amdgcn_ds_bpermute(ridx, __double2hiint(xm)),
+                                               __builtin_amdgcn_ds_bpermute(ridx, __double2loint(xm)));
+          xs = (rstar >= 17 && rstar <= 20) ? xrev : xs;
+          const bool okq = (rstar == 0) ? (hq != 0) : ((rstar == 16) ? (hq == 0) : ((rstar == 24) ? (hq <= 1) : (rstar < 24)));
+          const int bins_before = (rstar < 16) ? 32 * rstar - (rstar > 0 ? 1 : 0) : ((rstar == 16) ? 511 : 512 + 32 * (rstar - 17));
           xs = okq ? xs : 0.0;
           const double run = halfwave_scan_incl(xs);
           const unsigned long long mrow = __ballot(okq && (before + run) < pivot);
@@ -1036,7 +1098,7 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
 
 #pragma unroll
           for (int r = 0; r < 32; ++r) w[r] = table_load2(win_rs, q16, 512 * r);
-          if constexpr (LO_LDS) dma_hop<kLoNt>(dsrc + (size_t)min(fi + 1, last_d) * kHop - kHop, plane_lds + 8192);
+          if constexpr (LO_LDS) dma_hop<true>(dsrc + (size_t)min(fi + 1, last_d) * kHop - kHop, plane_lds + 8192);
         }
         if (fi & 1) finish_mfcc32<FEAT == 0>(mel_acc, recp, left, stride2, dct, logc, lane, plane_bytes + 8192);
         AFX_STAMP(9);   // log + DCT + store (every second iteration)
@@ -1132,7 +1194,7 @@ int frames32_class(uint32_t mask) {
 
 template <int FEAT, bool SCALED>
 static hipError_t launch_frames32_class(const FrameArgs& a, int grid_blocks, hipStream_t stream) {
-  constexpr int lds = Lds32<kMel32Rows>::total;
+  constexpr int lds = Lds32::total;
   auto k = frames32_kernel<FEAT, SCALED>;
   static bool attribute_set[16] = {};   // per device: raising the dynamic LDS limit once is enough
   int dev = 0;
@@ -1146,35 +1208,41 @@ static hipError_t launch_frames32_class(const FrameArgs& a, int grid_blocks, hip
   return hipGetLastError();
 }
 
+// The code object holds the kernels in the order of their first use, and that order numbers their labels: this is the
+// order in which the launcher's ternary ladder used to name them, kept so that the device code stays byte-identical
+#define L32(FEAT, SCALED) launch_frames32_class<FEAT, SCALED>
+[[maybe_unused]] static hipError_t (*const kFirstUse32[])(const FrameArgs&, int, hipStream_t) = {
+    L32(0, true), L32(0, false), L32(4, true), L32(4, false), L32(6, true), L32(6, false), L32(5, true),
+    L32(5, false), L32(1, true), L32(2, true), L32(3, true), L32(1, false), L32(2, false), L32(3, false)};
+#undef L32
+
+// the instantiations by (class launched, scaled), and whether stats32_finish_kernel follows
+struct Launch32 {
+  hipError_t (*launch[2])(const FrameArgs&, int, hipStream_t);
+  bool finish;
+};
+template <int FEAT>
+constexpr Launch32 launch32_of() { return {{launch_frames32_class<FEAT, false>, launch_frames32_class<FEAT, true>}, Class32<FEAT>::STATS}; }
+constexpr Launch32 kLaunch32[7] = {launch32_of<0>(), launch32_of<1>(), launch32_of<2>(), launch32_of<3>(), launch32_of<4>(), launch32_of<5>(), launch32_of<6>()};
+
 // f64 arithmetic, f32 PCM (scaled: the LoadSample front end's float signal times the buffer's FinalScaling): the
 // MFCC-only class, or the statistics class (a.mask has bits 1..7, a.stat_tmp holds total_frames x 8 doubles) followed
 // by its closed-form kernel
 hipError_t launch_frames32(const FrameArgs& a, int grid_blocks, hipStream_t stream, int64_t total_frames, bool scaled) {
   if (a.n_chunks <= 0) return hipSuccess;
-  const int cls = frames32_class(a.mask);
-  if (cls == 0) return scaled ? launch_frames32_class<0, true>(a, grid_blocks, stream) : launch_frames32_class<0, false>(a, grid_blocks, stream);
-  if (cls == 4) {
-    // Class 6 (no upper spectrum) where nobody reads bins above 768 -- and where it was measured to pay: batches of 160 000
-    // frames and more (C4-shaped files: -5 % at 160 k frames, -7 % from 320 k to 5.12 M).  The 82 000 frames of BASELINE's C3
-    // (1 000 two-second files) run 15 % SLOWER on it and 80 000 frames of one-second files 3 % faster (not understood:
-    // profiles/r06/ab_class6.txt); the stored values are the same either way, so the choice is free.
-    constexpr int64_t kClass6Frames = 131072;
-    if ((a.mask & kFramesWholeSpectrum) || total_frames < kClass6Frames)
-      return scaled ? launch_frames32_class<4, true>(a, grid_blocks, stream) : launch_frames32_class<4, false>(a, grid_blocks, stream);
-    return scaled ? launch_frames32_class<6, true>(a, grid_blocks, stream) : launch_frames32_class<6, false>(a, grid_blocks, stream);
-  }
-  hipError_t e;
-  if (cls == 1 && !(a.mask & 0x30u))   // neither skewness nor kurtosis: no third / fourth moments
-    e = scaled ? launch_frames32_class<5, true>(a, grid_blocks, stream) : launch_frames32_class<5, false>(a, grid_blocks, stream);
-  else if (scaled)
-    e = (cls == 1) ? launch_frames32_class<1, true>(a, grid_blocks, stream)
-                   : (cls == 2 ? launch_frames32_class<2, true>(a, grid_blocks, stream) : launch_frames32_class<3, true>(a, grid_blocks, stream));
-  else
-    e = (cls == 1) ? launch_frames32_class<1, false>(a, grid_blocks, stream)
-                   : (cls == 2 ? launch_frames32_class<2, false>(a, grid_blocks, stream) : launch_frames32_class<3, false>(a, grid_blocks, stream));
-  if (e != hipSuccess) return e;
+  int feat = frames32_class(a.mask);
+  if (feat == 1 && !(a.mask & 0x30u)) feat = 5;   // neither skewness nor kurtosis: no third / fourth moments
+  // Class 6 (no upper spectrum) where nobody reads bins above 768 -- and where it was measured to pay: batches of 160 000
+  // frames and more (C4-shaped files: -5 % at 160 k frames, -7 % from 320 k to 5.12 M).  The 82 000 frames of BASELINE's C3
+  // (1 000 two-second files) run 15 % SLOWER on it and 80 000 frames of one-second files 3 % faster (not understood:
+  // profiles/r06/ab_class6.txt); the stored values are the same either way, so the choice is free.
+  constexpr int64_t kClass6Frames = 131072;
+  if (feat == 4 && !(a.mask & kFramesWholeSpectrum) && total_frames >= kClass6Frames) feat = 6;
+  const hipError_t e = kLaunch32[feat].launch[scaled](a, grid_blocks, stream);
+  if (e != hipSuccess || !kLaunch32[feat].finish) return e;
   return launch_stats32_finish(a, stream, total_frames);
 }
+
 
 hipError_t launch_stats32_finish(const FrameArgs& a, hipStream_t stream, int64_t total_frames) {
   if (total_frames <= 0) return hipSuccess;

@@ -5,6 +5,8 @@
 #include <stdint.h>
 
 namespace afx {
+// internal bit of FrameArgs::mask: a consumer of the stored magnitudes needs bins above 768 too (the whitening follower
+// and the fail-safe f0 of afx_whiten.hip, the magnitude output) -- the half-wave full class then produces them
 constexpr uint32_t kFramesWholeSpectrum = 1u << 31;
 // internal bit of FrameArgs::mask: bands_kernel runs for this batch anyway and takes the spectral statistics (bits 1..7)
 // from the stored magnitudes; the half-wave frame kernel then only stores them (its magnitude class)
@@ -153,9 +155,10 @@ hipError_t launch_frames32(const FrameArgs& a, int grid_blocks, hipStream_t stre
 hipError_t launch_stats32_finish(const FrameArgs& a, hipStream_t stream, int64_t total_frames);
 int frames32_waves_per_block();
 int frames32_stat_tmp_doubles();
-int frames32_class(uint32_t frames_mask);   // 0 = MFCC only, 1 = + spectral statistics, 2 = full (bins 0..768 stored, amplitude), 3 = full, whole spectrum
-// internal bit of FrameArgs::mask: a consumer of the stored magnitudes needs bins above 768 too (the whitening follower
-// and the fail-safe f0 of afx_whiten.hip, the magnitude output) -- the half-wave full class then produces them
+// class of a mask: 0 = MFCC only, 1 = + spectral statistics, 2 = full (bins 0..768 stored, amplitude), 3 = full, whole
+// spectrum, 4 = magnitude class (kFramesStatsLater).  launch_frames32 runs class 5 for a class-1 mask without skewness /
+// kurtosis and class 6 for a large class-4 batch that nobody reads above bin 768 (the table in afx_frames32.hip)
+int frames32_class(uint32_t frames_mask);
 int frames_feature_class(uint32_t mask);     // 0 = MFCC only, 1 = + statistics, 2 = everything
 
 // Work queue of a persistent-grid launch: a wave starts with the item of its own index and draws every further one from
