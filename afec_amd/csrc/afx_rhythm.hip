@@ -29,8 +29,9 @@
 #pragma clang fp contract(off)
 
 // waves per SIMD the kernels are compiled for (A/B on MI355X, many-file workloads: 2 / 3 -> 3 / 6 waves: -18 % time;
-// the onset kernel then holds 168 VGPRs with 32 B of scratch, the post kernel 80 VGPRs with 384 B -- its VALU pipe is
-// only ~15 % busy, what it needs is more workgroups in flight to hide the barrier and memory latencies)
+// what every kernel then holds in registers, scratch and LDS is recorded in tests/golden/kernel_resources.json -- the
+// post kernel's VALU pipe is only ~15 % busy, what it needs is more workgroups in flight to hide the barrier and memory
+// latencies)
 constexpr int kOnsetWavesPerSimd = 3, kPostWavesPerSimd = 6;
 
 namespace afx {
@@ -478,10 +479,9 @@ __global__ __launch_bounds__(256, kOnsetWavesPerSimd) void onset_terms_kernel(Rh
   }
 }
 
-// ---- post kernel helpers ----------------------------------------------------------------------------------------
+// ---- post kernel: its records, its helpers, its stages in the order the kernel calls them -------------------------
 
 constexpr int kStage = 1024;
-constexpr int kMaxLdsFrames = kRhythmLdsFrames;
 
 // sum of gen(0) .. gen(n-1) accumulated in index order (TStatistics::Sum, Statistics.cpp:236-245; fvec_sum): the terms are
 // produced by all threads, one lane adds them.  Every thread gets the result.
@@ -566,355 +566,475 @@ __device__ __forceinline__ double key_value(unsigned long long k) {
   return __longlong_as_double((long long)u);
 }
 
-__global__ __launch_bounds__(256, kPostWavesPerSimd) void rhythm_post_kernel(RhythmArgs a) {
-  __shared__ __align__(16) double s_stage[kStage];
-  __shared__ double s_result[2];
-  __shared__ float s_win[520];
-  extern __shared__ double s_series[];     // the sharpened onsets of the file, de-interleaved by 4, when they fit
-  __shared__ float s_post[257];
-  __shared__ float s_vlo[256], s_vhi[256];
-  __shared__ unsigned long long s_mask[4];
-  __shared__ int s_wsum[4];
-  __shared__ unsigned s_flagbits[kStage / 32];
-  __shared__ unsigned s_hist[256];
-  __shared__ int s_int[4];
-  __shared__ unsigned long long s_key;
-  // one workgroup per (file, onset function): the two chains of a file are independent up to the final tempo, which
-  // rhythm_final_kernel derives from both (a lone long file is latency-bound: two workgroups halve its time)
-  const RhythmFile f = a.files[blockIdx.x >> 1];
-  const int T = f.frames, tid = threadIdx.x;
-  double* out = a.scalars + (int64_t)(blockIdx.x >> 1) * 14;
-  if (T <= 0) {
-    if (tid < 6) out[6 * (blockIdx.x & 1) + tid] = 0.0;
-    if (tid == 0) out[12 + (blockIdx.x & 1)] = 0.0;
-    return;
+// The static LDS of rhythm_post_kernel, declared once there.  Every scalar that crosses a barrier has a member of its own
+// (one writer stage, named beside it); no member is shared between stages but `stage` and the union, as their comments say.
+struct PostLds {
+  struct Detect {                      // detect_onsets, per chunk of 256 frames:
+    float win[520];                    //   the onset function of the chunk behind the medspan - 1 values before it
+    float vlo[256], vhi[256];          //   lower and upper median of every frame's span
+    float post[256];                   //   onset function less median (mOdfvalpost)
+    unsigned long long mask[4];        //   per wave: the candidates, then what the gap rule left of them
+  };
+  struct Contrast {                    // order_statistic and valley_walk:
+    unsigned hist[256];                //   the radix select's digit counts of one pass
+    int wave_sum[4];                   //   their sums per wave
+    unsigned flagbits[kStage / 32];    //   valley_walk, one bit per staged frame: a window peak at or above the threshold
+  };
+  // serial_sum's terms and valley_walk's values.  Both fill it behind a barrier of their own and are done with it at one;
+  // no other stage touches it.
+  alignas(16) double stage[kStage];
+  union {                              // detect_onsets has returned, behind its last barrier, before order_statistic starts
+    Detect detect;
+    Contrast contrast;
+  };
+  double sum;                          // serial_sum: thread 0's total for every thread
+  double tempo, confidence;            // track_beats: thread 0's results for every thread
+  double argmax_value[4];              // last_argmax: the four waves' candidates ...
+  unsigned argmax_index[4];            //   ... and where they stand
+  unsigned long long select_prefix;    // order_statistic: the digits fixed so far, from pass to pass
+  int select_rank;                     // order_statistic: the rank looked for among the keys that share the prefix
+  unsigned argmax;                     // last_argmax: the position every thread reads
+  // state and counters that a stage adds to; the kernel zeroes the five before its first barrier
+  float carried_post;                  // detect_onsets, from chunk to chunk: mOdfvalpostprev of the next chunk's first frame
+  int next_allowed;                    // detect_onsets, from chunk to chunk: the first frame the gap rule lets the next onset have
+  int onset_count;                     // detect_onsets: OnsetCount
+  int peak_count, last_loud;           // window_peaks: window peaks above MPeakThreshold; the last frame not below it
+};
+
+// what every stage of one (file, onset function) reads; the rows are the function's of RhythmArgs::scratch at the file
+struct PostChain {
+  int T, type;     // frames of the file; 0: complex, 1: power
+  double* raw;     // TRhythmTracker::Onsets: detect_onsets writes it, canny_sharpen (and rhythm_final_kernel) read it
+  double* S;       // SharpenedOnsets: canny_sharpen writes it, every later stage reads it
+  double* W;       // canny_sharpen: the convolution; track_beats: the autocorrelation; from window_peaks on: 1.0 where the
+                   // frame is a window peak, else 0.0
+  double* AO;      // track_beats: the weighted comb filterbank output [T / 4]
+};
+
+// Median of every span of `med` values by rank, for the m frames of a chunk staged in d.win: element e of the staged
+// values is the rank-r value of a span when fewer than r + 1 values of the span lie below it and more than r do not exceed
+// it.  Its rank is counted once for the first span that holds it and updated by the value that leaves and the one that
+// enters for the next ones.  -> d.vlo, d.vhi
+__device__ __forceinline__ void sliding_median_by_rank(PostLds::Detect& d, int m, int med) {
+  const int r_hi = med >> 1, r_lo = (med & 1) ? r_hi : r_hi - 1;   // sorted[(med-1)>>1] for odd spans
+  for (int e = threadIdx.x; e < m + med - 1; e += 256) {
+    const float c = d.win[e];
+    const int fi0 = max(0, e - (med - 1)), fi1 = min(m - 1, e);
+    int lt = 0, le = 0;
+    for (int k = 0; k < med; ++k) {
+      const float w = d.win[fi0 + k];
+      lt += (w < c) ? 1 : 0;
+      le += (w <= c) ? 1 : 0;
+    }
+    for (int fi = fi0; fi <= fi1; ++fi) {
+      if (lt <= r_lo && r_lo < le) d.vlo[fi] = c;
+      if (lt <= r_hi && r_hi < le) d.vhi[fi] = c;
+      if (fi < fi1) {
+        const float gone = d.win[fi], come = d.win[fi + med];
+        lt += ((come < c) ? 1 : 0) - ((gone < c) ? 1 : 0);
+        le += ((come <= c) ? 1 : 0) - ((gone <= c) ? 1 : 0);
+      }
+    }
   }
-  const int64_t tot = a.total_frames;
-  const int rate = a.sample_rate;
-  double tempo[2] = {0.0, 0.0}, conf[2] = {0.0, 0.0};
-  int last_loud[2] = {0, 0};
+}
 
-  {
-    const int type = blockIdx.x & 1;
-    double* raw = a.scratch + (int64_t)(0 + type) * tot + f.frame0;   // TRhythmTracker::Onsets
-    double* S = a.scratch + (int64_t)(2 + type) * tot + f.frame0;     // SharpenedOnsets
-    double* W = a.scratch + (int64_t)(4 + type) * tot + f.frame0;     // convolution, then the autocorrelation, then flags
-    double* AO = a.scratch + (int64_t)(6 + type) * tot + f.frame0;    // comb filterbank output [T / 4]
-    double* o6 = out + 6 * type;
-    const float* odf = a.odf + f.frame0 * 2 + type;
-    const float thresh = a.thresh[type];
-    const int med = a.medspan, mingap = a.mingap[type];
-
-    // ---- DetectOnset (OD.cpp:549-587): median of the last `med` onset-function values removed, then the gap rule ----
-    if (tid == 0) { s_post[256] = 0.f; s_int[0] = 0; s_int[1] = 0; }   // mOdfvalpost = 0, mGapLeft = 0, onset count
-    __syncthreads();
-    for (int c0 = 0; c0 < T; c0 += 256) {
-      const int m = min(256, T - c0);
-      for (int i = tid; i < 256 + med; i += 256) {
-        const int fr = c0 - (med - 1) + i;
-        s_win[i] = (fr >= 0 && fr < T) ? odf[(int64_t)fr * 2] : 0.f;
-      }
-      __syncthreads();
-      // Median of every span by rank: element e of the staged values is the rank-r value of a span when fewer than
-      // r + 1 values of the span lie below it and more than r do not exceed it.  Its rank is counted once for the first
-      // span that holds it and updated by the value that leaves and the one that enters for the next ones.
-      const int r_hi = med >> 1, r_lo = (med & 1) ? r_hi : r_hi - 1;   // sorted[(med-1)>>1] for odd spans
-      for (int e = tid; e < m + med - 1; e += 256) {
-        const float c = s_win[e];
-        const int fi0 = max(0, e - (med - 1)), fi1 = min(m - 1, e);
-        int lt = 0, le = 0;
-        for (int k = 0; k < med; ++k) {
-          const float w = s_win[fi0 + k];
-          lt += (w < c) ? 1 : 0;
-          le += (w <= c) ? 1 : 0;
-        }
-        for (int fi = fi0; fi <= fi1; ++fi) {
-          if (lt <= r_lo && r_lo < le) s_vlo[fi] = c;
-          if (lt <= r_hi && r_hi < le) s_vhi[fi] = c;
-          if (fi < fi1) {
-            const float gone = s_win[fi], come = s_win[fi + med];
-            lt += ((come < c) ? 1 : 0) - ((gone < c) ? 1 : 0);
-            le += ((come <= c) ? 1 : 0) - ((gone <= c) ? 1 : 0);
-          }
-        }
-      }
-      __syncthreads();
-      float post = 0.f;
-      if (tid < m) {
-        const float v_lo = s_vlo[tid], v_hi = s_vhi[tid];
-        const float median = (med & 1) ? v_hi : ((v_hi + v_lo) * 0.5f);
-        post = s_win[tid + med - 1] - median;      // this frame's value is the newest of its span
-        s_post[tid] = post;
-      }
-      const float carried = s_post[256];        // mOdfvalpostprev of the chunk's first frame
-      __syncthreads();
-      {
-        // candidates (post > thresh, previous <= thresh) as one 64-bit mask per wave; the gap rule (mGapLeft) walks the
-        // set bits only: after a detection at frame p the next one is allowed from frame p + mingap + 1
-        const float prev = (tid == 0) ? carried : s_post[(tid > 0) ? tid - 1 : 0];
-        const bool cand = (tid < m) && (post > thresh) && (prev <= thresh);
-        const unsigned long long mask = __ballot(cand);
-        if ((tid & 63) == 0) s_mask[tid >> 6] = mask;
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int next_allowed = s_int[0];
-        for (int w = 0; w < 4; ++w) {
-          unsigned long long mk = s_mask[w], det = 0;
-          while (mk) {
-            const int bit = __ffsll((long long)mk) - 1;
-            mk &= mk - 1;
-            const int fr = c0 + 64 * w + bit;
-            if (fr >= next_allowed) { det |= 1ull << bit; next_allowed = fr + mingap + 1; }
-          }
-          s_mask[w] = det;
-        }
-        s_int[0] = next_allowed;
-        s_post[256] = s_post[m - 1];
-      }
-      __syncthreads();
-      if (tid < m) {
-        const double v = ((s_mask[tid >> 6] >> (tid & 63)) & 1) ? (double)post : 0.0;     // RT.cpp:109-118
-        raw[c0 + tid] = v;
-        a.onsets[(f.frame0 + c0 + tid) * 2 + type] = v;
-        if (v > (type == 0 ? 0.2 : 0.8)) atomicAdd(&s_int[1], 1);   // OnsetCount, RT.cpp:124-137
-      }
-      __syncthreads();
+// The gap rule (mGapLeft) over the candidates of the chunk at frame c0, by one thread: it walks the set bits only; after a
+// detection at frame p the next one is allowed from frame p + mingap + 1.  Leaves the detections in d.mask and the state
+// the next chunk starts from.
+__device__ __forceinline__ void gap_walk(PostLds& lds, int c0, int m, int mingap) {
+  int next_allowed = lds.next_allowed;
+  for (int w = 0; w < 4; ++w) {
+    unsigned long long mk = lds.detect.mask[w], det = 0;
+    while (mk) {
+      const int bit = __ffsll((long long)mk) - 1;
+      mk &= mk - 1;
+      const int fr = c0 + 64 * w + bit;
+      if (fr >= next_allowed) { det |= 1ull << bit; next_allowed = fr + mingap + 1; }
     }
-    const int count = s_int[1];
-    __syncthreads();
+    lds.detect.mask[w] = det;
+  }
+  lds.next_allowed = next_allowed;
+  lds.carried_post = lds.detect.post[m - 1];
+}
 
-    // ---- TCannyWindow::Apply (CW.cpp:27-68) ----
-    for (int i = tid; i < T; i += 256) {
-      double sum = 0.0;
-      for (int s = -12; s < 12; ++s)
-        if (i + s >= 0 && i + s < T) sum += raw[i + s] * a.canny[s + 12];
-      W[i] = sum;
+// DetectOnset (OD.cpp:549-587): median of the last `med` onset-function values removed, then the gap rule; the onsets go
+// to c.raw and RhythmArgs::onsets.  -> OnsetCount (RT.cpp:124-137)
+__device__ __forceinline__ int detect_onsets(const RhythmArgs& a, const RhythmFile& f, const PostChain& c, PostLds& lds) {
+  const int tid = threadIdx.x, T = c.T, type = c.type;
+  PostLds::Detect& d = lds.detect;
+  const float* odf = a.odf + f.frame0 * 2 + type;
+  const float thresh = a.thresh[type];
+  const int med = a.medspan, mingap = a.mingap[type];
+  for (int c0 = 0; c0 < T; c0 += 256) {
+    const int m = min(256, T - c0);
+    for (int i = tid; i < 256 + med; i += 256) {
+      const int fr = c0 - (med - 1) + i;
+      d.win[i] = (fr >= 0 && fr < T) ? odf[(int64_t)fr * 2] : 0.f;
     }
     __syncthreads();
-    const double w_first = W[0];
-    const double mean = mean_of(serial_sum(T, [&](int i) { return W[i]; }, s_stage, s_result), T, w_first);
-    const double var = (T >= 2) ? serial_sum(T, [&](int i) { return (W[i] - mean) * (W[i] - mean); }, s_stage, s_result) / T : 0.0;
+    sliding_median_by_rank(d, m, med);
+    __syncthreads();
+    float post = 0.f;
+    if (tid < m) {
+      const float v_lo = d.vlo[tid], v_hi = d.vhi[tid];
+      const float median = (med & 1) ? v_hi : ((v_hi + v_lo) * 0.5f);
+      post = d.win[tid + med - 1] - median;      // this frame's value is the newest of its span
+      d.post[tid] = post;
+    }
+    const float carried = lds.carried_post;      // mOdfvalpostprev of the chunk's first frame
+    __syncthreads();
     {
-      const double sd = sqrt(var);
-      for (int i = tid; i < T; i += 256) {
-        double z = W[i];
-        if (var > 0.0) {
-          z = (z - mean) / sd;
-          z = (0.0 > z) ? 0.0 : z;
-        }
-        S[i] = z;
-      }
+      // candidates (post > thresh, previous <= thresh) as one 64-bit mask per wave
+      const float prev = (tid == 0) ? carried : d.post[(tid > 0) ? tid - 1 : 0];
+      const bool cand = (tid < m) && (post > thresh) && (prev <= thresh);
+      const unsigned long long mask = __ballot(cand);
+      if ((tid & 63) == 0) d.mask[tid >> 6] = mask;
     }
-    if (tid == 0) s_int[2] = 0;
     __syncthreads();
-
-    // ---- CalculateTempo (RT.cpp:159-234): one aubio_beattracking_do on a fresh tracker (bt.c:132-186, 273-404) ----
-    if (count >= 4) {
-      const unsigned laglen = (unsigned)T / 4;
-      const int plane = (a.lds_frames + 3) >> 2;
-      if (T <= a.lds_frames) {
-        for (int i = tid; i < T; i += 256) s_series[(i & 3) * plane + (i >> 2)] = S[i];
-        __syncthreads();
-        autocorrelation<true>(S, s_series, plane, T, W);
-      } else autocorrelation<false>(S, s_series, plane, T, W);
-      __syncthreads();
-      const double ray = 60. * rate / 120. / kRtHop;           // bt.c:65
-      for (unsigned i = tid; i < laglen; i += 256) {
-        double acc = 0.0;
-        if (i >= 1 && i + 1 < laglen)                          // comb filterbank, bt.c:165-172
-          for (unsigned aa = 1; aa <= 4; ++aa)
-            for (unsigned b = 1; b < 2 * aa; ++b) acc += W[i * aa + b - 1] * 1. / (2. * aa - 1.);
-        const double rw = ((int)i < a.rayleigh_n)                // Rayleigh weight, bt.c:105-108, 174
-                              ? a.rayleigh[i]
-                              : ((double)(i + 1.) / (ray * ray)) * exp((-((i + 1.) * (i + 1.)) / (2. * (ray * ray))));
-        AO[i] = acc * rw;
-      }
-      __syncthreads();
-      // fvec_max_elem (mathutils.c:268-283) starts from 0 and lets later equals win: the last index holding max(0, max)
-      {
-        double best = 0.0;
-        int pos = 0;
-        for (unsigned i = tid; i < laglen; i += 256) {
-          const double d = AO[i];
-          if (!(best > d)) { best = d; pos = (int)i; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {       // larger value wins, the later index among equals
-          const double d = __shfl_xor(best, o);
-          const int p = __shfl_xor(pos, o);
-          if (d > best || (d == best && p > pos)) { best = d; pos = p; }
-        }
-        if ((tid & 63) == 0) { s_stage[tid >> 6] = best; s_hist[tid >> 6] = (unsigned)pos; }
-        __syncthreads();
-        if (tid == 0) {
-          double bv = 0.0;
-          unsigned bp = 0;
-          for (int t = 0; t < 4; ++t) {
-            const double d = s_stage[t];
-            const unsigned p = s_hist[t];
-            if (d > bv || (d == bv && p > bp)) { bv = d; bp = p; }
-          }
-          s_int[3] = (int)bp;
-        }
-        __syncthreads();
-      }
-      const unsigned maxindex = (unsigned)s_int[3];
-      __syncthreads();
-      const double acf_sum = serial_sum((int)laglen, [&](int i) { return AO[i]; }, s_stage, s_result);
-      if (tid == 0) {
-        double rp;
-        if (maxindex > 0 && laglen > 0 && maxindex < laglen - 1) {   // fvec_quadratic_peak_pos, mathutils.c:494-506
-          const double s0 = AO[maxindex - 1], s1 = AO[maxindex], s2 = AO[maxindex + 1];
-          rp = maxindex + .5 * (s0 - s2) / (s0 - 2. * s1 + s2);
-        } else rp = (double)(unsigned)ray;                     // p->rayparam is uint_t, bt.c:46, 82
-        double bp = rp;                                        // checkstate on the fresh state, bt.c:362-379
-        while (0 < bp && bp < 25) bp = bp * 2;
-        double bpm = (bp != 0) ? 60. / (kRtHop * bp / (double)rate) : 0.;
-        double cf = 0.;                                        // bt.c:435-444
-        if (acf_sum != 0.) {                                   // fvec_quadratic_peak_mag, mathutils.c:508-517
-          double mag = 0.;
-          if (!(rp >= laglen || rp < 0.)) {
-            const unsigned index = (unsigned)(rp - .5) + 1;
-            if ((double)index == rp) mag = AO[index];
-            else mag = AO[index] - .25 * (AO[index - 1] - AO[index + 1]) * (rp - index);
-          }
-          cf = mag / acf_sum;
-        }
-        cf = cf * 16.0;
-        cf = (cf < 0.0) ? 0.0 : ((cf > 1.0) ? 1.0 : cf);
-        if (bpm < 20.0 || bpm > 300.0) { cf = 0.0; bpm = 0.0; }
-        else {
-          while (bpm < 80.0) bpm *= 2.0;
-          while (bpm >= 200.0) bpm /= 2.0;
-        }
-        s_result[0] = bpm;
-        s_result[1] = cf;
-      }
-      __syncthreads();
-      tempo[type] = s_result[0];
-      conf[type] = s_result[1];
-      __syncthreads();
+    if (tid == 0) gap_walk(lds, c0, m, mingap);
+    __syncthreads();
+    if (tid < m) {
+      const double v = ((d.mask[tid >> 6] >> (tid & 63)) & 1) ? (double)post : 0.0;     // RT.cpp:109-118
+      c.raw[c0 + tid] = v;
+      a.onsets[(f.frame0 + c0 + tid) * 2 + type] = v;
+      if (v > (type == 0 ? 0.2 : 0.8)) atomicAdd(&lds.onset_count, 1);   // OnsetCount, RT.cpp:124-137
     }
+    __syncthreads();
+  }
+  const int count = lds.onset_count;
+  __syncthreads();
+  return count;
+}
 
-    // ---- peaks of the sharpened onsets (RT.cpp:624-660): W <- 1 where no larger value lies within +-24 frames ----
+// TCannyWindow::Apply (CW.cpp:27-68): c.raw -> c.S, by way of the convolution in c.W
+__device__ __forceinline__ void canny_sharpen(const RhythmArgs& a, const PostChain& c, PostLds& lds) {
+  const int tid = threadIdx.x, T = c.T;
+  double* W = c.W;
+  for (int i = tid; i < T; i += 256) {
+    double sum = 0.0;
+    for (int s = -12; s < 12; ++s)
+      if (i + s >= 0 && i + s < T) sum += c.raw[i + s] * a.canny[s + 12];
+    W[i] = sum;
+  }
+  __syncthreads();
+  const double w_first = W[0];
+  const double mean = mean_of(serial_sum(T, [&](int i) { return W[i]; }, lds.stage, &lds.sum), T, w_first);
+  const double var = (T >= 2) ? serial_sum(T, [&](int i) { return (W[i] - mean) * (W[i] - mean); }, lds.stage, &lds.sum) / T : 0.0;
+  const double sd = sqrt(var);
+  for (int i = tid; i < T; i += 256) {
+    double z = W[i];
+    if (var > 0.0) {
+      z = (z - mean) / sd;
+      z = (0.0 > z) ? 0.0 : z;
+    }
+    c.S[i] = z;
+  }
+  __syncthreads();
+}
+
+// fvec_max_elem (mathutils.c:268-283) starts from 0 and lets later equals win: the last index holding max(0, max) of x[0..n)
+__device__ __forceinline__ unsigned last_argmax(const double* x, unsigned n, PostLds& lds) {
+  const int tid = threadIdx.x;
+  double best = 0.0;
+  int pos = 0;
+  for (unsigned i = tid; i < n; i += 256) {
+    const double d = x[i];
+    if (!(best > d)) { best = d; pos = (int)i; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {       // larger value wins, the later index among equals
+    const double d = __shfl_xor(best, o);
+    const int p = __shfl_xor(pos, o);
+    if (d > best || (d == best && p > pos)) { best = d; pos = p; }
+  }
+  if ((tid & 63) == 0) { lds.argmax_value[tid >> 6] = best; lds.argmax_index[tid >> 6] = (unsigned)pos; }
+  __syncthreads();
+  if (tid == 0) {
+    double bv = 0.0;
+    unsigned bp = 0;
+    for (int t = 0; t < 4; ++t) {
+      const double d = lds.argmax_value[t];
+      const unsigned p = lds.argmax_index[t];
+      if (d > bv || (d == bv && p > bp)) { bv = d; bp = p; }
+    }
+    lds.argmax = bp;
+  }
+  __syncthreads();
+  const unsigned at = lds.argmax;
+  __syncthreads();
+  return at;
+}
+
+// CalculateTempo (RT.cpp:159-234): one aubio_beattracking_do on a fresh tracker (bt.c:132-186, 273-404) over c.S.
+// series: the dynamic LDS, where the file's sharpened onsets are staged, de-interleaved by 4, when they fit.
+__device__ __forceinline__ void track_beats(const RhythmArgs& a, const PostChain& c, PostLds& lds, double* series, double& tempo,
+                                            double& confidence) {
+  const int tid = threadIdx.x, T = c.T;
+  double *W = c.W, *AO = c.AO;
+  const unsigned laglen = (unsigned)T / 4;
+  const int plane = (a.lds_frames + 3) >> 2;
+  if (T <= a.lds_frames) {
+    for (int i = tid; i < T; i += 256) series[(i & 3) * plane + (i >> 2)] = c.S[i];
+    __syncthreads();
+    autocorrelation<true>(c.S, series, plane, T, W);
+  } else autocorrelation<false>(c.S, series, plane, T, W);
+  __syncthreads();
+  const double ray = 60. * a.sample_rate / 120. / kRtHop;    // bt.c:65
+  for (unsigned i = tid; i < laglen; i += 256) {
+    double acc = 0.0;
+    if (i >= 1 && i + 1 < laglen)                          // comb filterbank, bt.c:165-172
+      for (unsigned aa = 1; aa <= 4; ++aa)
+        for (unsigned b = 1; b < 2 * aa; ++b) acc += W[i * aa + b - 1] * 1. / (2. * aa - 1.);
+    const double rw = ((int)i < a.rayleigh_n)                // Rayleigh weight, bt.c:105-108, 174
+                          ? a.rayleigh[i]
+                          : ((double)(i + 1.) / (ray * ray)) * exp((-((i + 1.) * (i + 1.)) / (2. * (ray * ray))));
+    AO[i] = acc * rw;
+  }
+  __syncthreads();
+  const unsigned maxindex = last_argmax(AO, laglen, lds);
+  const double acf_sum = serial_sum((int)laglen, [&](int i) { return AO[i]; }, lds.stage, &lds.sum);
+  if (tid == 0) {      // the peak, the tempo it stands for and its confidence
+    double rp;
+    if (maxindex > 0 && laglen > 0 && maxindex < laglen - 1) {   // fvec_quadratic_peak_pos, mathutils.c:494-506
+      const double s0 = AO[maxindex - 1], s1 = AO[maxindex], s2 = AO[maxindex + 1];
+      rp = maxindex + .5 * (s0 - s2) / (s0 - 2. * s1 + s2);
+    } else rp = (double)(unsigned)ray;                     // p->rayparam is uint_t, bt.c:46, 82
+    double bp = rp;                                        // checkstate on the fresh state, bt.c:362-379
+    while (0 < bp && bp < 25) bp = bp * 2;
+    double bpm = (bp != 0) ? 60. / (kRtHop * bp / (double)a.sample_rate) : 0.;
+    double cf = 0.;                                        // bt.c:435-444
+    if (acf_sum != 0.) {                                   // fvec_quadratic_peak_mag, mathutils.c:508-517
+      double mag = 0.;
+      if (!(rp >= laglen || rp < 0.)) {
+        const unsigned index = (unsigned)(rp - .5) + 1;
+        if ((double)index == rp) mag = AO[index];
+        else mag = AO[index] - .25 * (AO[index - 1] - AO[index + 1]) * (rp - index);
+      }
+      cf = mag / acf_sum;
+    }
+    cf = cf * 16.0;
+    cf = (cf < 0.0) ? 0.0 : ((cf > 1.0) ? 1.0 : cf);
+    if (bpm < 20.0 || bpm > 300.0) { cf = 0.0; bpm = 0.0; }
+    else {
+      while (bpm < 80.0) bpm *= 2.0;
+      while (bpm >= 200.0) bpm /= 2.0;
+    }
+    lds.tempo = bpm;
+    lds.confidence = cf;
+  }
+  __syncthreads();
+  tempo = lds.tempo;
+  confidence = lds.confidence;
+  __syncthreads();
+}
+
+// peaks of the sharpened onsets (RT.cpp:624-660): c.W <- 1 where no larger value lies within +-24 frames; their number
+// above MPeakThreshold, and the last frame that is not below it (RT.cpp:264-268)
+__device__ __forceinline__ void window_peaks(const PostChain& c, PostLds& lds, int& n_peaks, int& last_loud) {
+  const int tid = threadIdx.x, T = c.T;
+  const double* S = c.S;
+  for (int i = tid; i < T; i += 256) {
+    c.W[i] = window_peak(S, T, i) ? 1.0 : 0.0;
+    if (i >= 1 && !(S[i] < 0.1)) atomicMax(&lds.last_loud, i);
+  }
+  __syncthreads();
+  last_loud = lds.last_loud;
+  for (int i = tid; i < T; i += 256)
+    if (S[i] > 0.1 && c.W[i] != 0.0) atomicAdd(&lds.peak_count, 1);
+  __syncthreads();
+  n_peaks = lds.peak_count;
+}
+
+// sorted(S)[k]: radix select on the order-preserving bit pattern, 8 bits per pass
+__device__ __forceinline__ double order_statistic(const double* S, int T, int k, PostLds& lds) {
+  const int tid = threadIdx.x;
+  PostLds::Contrast& h = lds.contrast;
+  unsigned long long prefix = 0;
+  for (int pass = 0; pass < 8; ++pass) {
+    const int shift = 56 - 8 * pass;
+    h.hist[tid] = 0;
+    __syncthreads();
     for (int i = tid; i < T; i += 256) {
-      W[i] = window_peak(S, T, i) ? 1.0 : 0.0;
-      if (i >= 1 && !(S[i] < 0.1)) atomicMax(&s_int[2], i);   // last frame that is not below MPeakThreshold, RT.cpp:264-268
+      const unsigned long long key = order_key(S[i]);
+      if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&h.hist[(key >> shift) & 255], 1u);
     }
-    if (tid == 0) s_int[1] = 0;
     __syncthreads();
-    last_loud[type] = s_int[2];
-    for (int i = tid; i < T; i += 256)
-      if (S[i] > 0.1 && W[i] != 0.0) atomicAdd(&s_int[1], 1);
-    __syncthreads();
-    const int n_peaks = s_int[1];
-    const double peak_sum = serial_sum(T, [&](int i) { return (S[i] > 0.1 && W[i] != 0.0) ? S[i] : 0.0; }, s_stage, s_result);
-    const double total_sum = serial_sum(T, [&](int i) { return S[i]; }, s_stage, s_result);
-
-    // ---- CalculateRhythmContrast (RT.cpp:325-412) ----
-    // threshold = sorted[(int)(0.85 (T - 1))]: radix select on the order-preserving bit pattern, 8 bits per pass
     {
-      int k = (int)(85.0 / 100.0 * (T - 1));
-      unsigned long long prefix = 0;
-      for (int pass = 0; pass < 8; ++pass) {
-        const int shift = 56 - 8 * pass;
-        s_hist[tid] = 0;
-        __syncthreads();
-        for (int i = tid; i < T; i += 256) {
-          const unsigned long long key = order_key(S[i]);
-          if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&s_hist[(key >> shift) & 255], 1u);
-        }
-        __syncthreads();
-        {
-          // the digit whose bin holds the k-th element: exclusive prefix sum of the 256 bins, one bin per thread
-          const int h = (int)s_hist[tid];
-          const int incl = wave_scan_incl(h);
-          if ((tid & 63) == 63) s_wsum[tid >> 6] = incl;
-          __syncthreads();
-          int before = 0;
-          for (int w = 0; w < (tid >> 6); ++w) before += s_wsum[w];
-          const int excl = before + incl - h;
-          if (h > 0 && excl <= k && k < excl + h) {
-            s_int[3] = k - excl;
-            s_key = prefix | ((unsigned long long)tid << shift);
-          }
-        }
-        __syncthreads();
-        k = s_int[3];
-        prefix = s_key;
-        __syncthreads();
+      // the digit whose bin holds the k-th element: exclusive prefix sum of the 256 bins, one bin per thread
+      const int n = (int)h.hist[tid];
+      const int incl = wave_scan_incl(n);
+      if ((tid & 63) == 63) h.wave_sum[tid >> 6] = incl;
+      __syncthreads();
+      int before = 0;
+      for (int w = 0; w < (tid >> 6); ++w) before += h.wave_sum[w];
+      const int excl = before + incl - n;
+      if (n > 0 && excl <= k && k < excl + n) {
+        lds.select_rank = k - excl;
+        lds.select_prefix = prefix | ((unsigned long long)tid << shift);
       }
-      const double threshold = key_value(prefix);
-      // serial walk with the running valley (RT.cpp:343-383)
-      if (tid == 0) { s_result[0] = 0.0; s_result[1] = 0.0; s_int[3] = 0; }
-      double valley_value = threshold, valley_at = S[0], psum = 0.0, vsum = 0.0;   // thread 0's copies are the live ones
-      int np = 0;
-      for (int c0 = 0; c0 < T; c0 += kStage) {
-        const int m = min(kStage, T - c0);
-        __syncthreads();
-        // stage the values and, one bit per frame, "at or above the threshold and a window peak"
-        for (int i = tid; i < kStage; i += 256) {
-          const bool in = i < m;
-          const double sv = in ? S[c0 + i] : 0.0;
-          s_stage[i] = sv;
-          const bool flag = in && !(sv < threshold) && W[c0 + i] != 0.0;
-          const unsigned long long bits = __ballot(flag);
-          if ((tid & 63) == 0) { s_flagbits[i >> 5] = (unsigned)bits; s_flagbits[(i >> 5) + 1] = (unsigned)(bits >> 32); }
-        }
-        __syncthreads();
-        if (tid == 0) {
-          for (int i0 = 0; i0 < m; i0 += 8) {
-            const double2 p0 = *reinterpret_cast<const double2*>(s_stage + i0), p1 = *reinterpret_cast<const double2*>(s_stage + i0 + 2),
-                          p2 = *reinterpret_cast<const double2*>(s_stage + i0 + 4), p3 = *reinterpret_cast<const double2*>(s_stage + i0 + 6);
-            const double xs[8] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y};
-            const unsigned fl = (s_flagbits[i0 >> 5] >> (i0 & 31)) & 0xFFu;
-            const int cnt = min(8, m - i0);
+    }
+    __syncthreads();
+    k = lds.select_rank;
+    prefix = lds.select_prefix;
+    __syncthreads();
+  }
+  return key_value(prefix);
+}
+
+// The serial walk of CalculateRhythmContrast with the running valley (RT.cpp:343-383) and, from its peaks and valleys, the
+// contrast (RT.cpp:325-412).  total_sum: the in-order sum of c.S.  Thread 0's result is the live one.
+__device__ __forceinline__ double valley_walk(const PostChain& c, double threshold, double total_sum, PostLds& lds) {
+  const int tid = threadIdx.x, T = c.T;
+  double* s_stage = lds.stage;
+  unsigned* s_flagbits = lds.contrast.flagbits;
+  double valley_value = threshold, valley_at = c.S[0], psum = 0.0, vsum = 0.0;
+  int np = 0;
+  for (int c0 = 0; c0 < T; c0 += kStage) {
+    const int m = min(kStage, T - c0);
+    __syncthreads();
+    // stage the values and, one bit per frame, "at or above the threshold and a window peak"
+    for (int i = tid; i < kStage; i += 256) {
+      const bool in = i < m;
+      const double sv = in ? c.S[c0 + i] : 0.0;
+      s_stage[i] = sv;
+      const bool flag = in && !(sv < threshold) && c.W[c0 + i] != 0.0;
+      const unsigned long long bits = __ballot(flag);
+      if ((tid & 63) == 0) { s_flagbits[i >> 5] = (unsigned)bits; s_flagbits[(i >> 5) + 1] = (unsigned)(bits >> 32); }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int i0 = 0; i0 < m; i0 += 8) {
+        const double2 p0 = *reinterpret_cast<const double2*>(s_stage + i0), p1 = *reinterpret_cast<const double2*>(s_stage + i0 + 2),
+                      p2 = *reinterpret_cast<const double2*>(s_stage + i0 + 4), p3 = *reinterpret_cast<const double2*>(s_stage + i0 + 6);
+        const double xs[8] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y};
+        const unsigned fl = (s_flagbits[i0 >> 5] >> (i0 & 31)) & 0xFFu;
+        const int cnt = min(8, m - i0);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
-              if (k < cnt) {
-                const double xv = xs[k];
-                if (xv < valley_value) { valley_at = xv; valley_value = xv; }
-                if ((fl >> k) & 1) {
-                  psum += xv;
-                  vsum += valley_at;
-                  ++np;
-                  valley_value = xv;
-                }
-              }
+        for (int k = 0; k < 8; ++k) {
+          if (k < cnt) {
+            const double xv = xs[k];
+            if (xv < valley_value) { valley_at = xv; valley_value = xv; }
+            if ((fl >> k) & 1) {
+              psum += xv;
+              vsum += valley_at;
+              ++np;
+              valley_value = xv;
             }
           }
         }
       }
-      if (tid == 0) {
-        const double total_mean = mean_of(total_sum, T, S[0]);
-        // Mean of a single-element list is the element; psum / vsum hold exactly that element then
-        const double peak_mean = mean_of(psum, np, psum);
-        const double valley_mean = mean_of(vsum, np, vsum) + 0.0001;
-        double contrast = 0.0;
-        if (peak_mean != 0.0) contrast = -1.0 * pow(peak_mean / valley_mean, 1.0 / log(total_mean + 0.0001));
-        o6[0] = (double)count;
-        o6[1] = tempo[type];
-        o6[2] = conf[type];
-        o6[3] = (double)n_peaks / (double)T * (double)kRtHop / (double)512;      // RT.cpp:288-289
-        double strength = 0.0;                                                  // RT.cpp:316-318
-        if (n_peaks) {
-          strength = mean_of(peak_sum, n_peaks, peak_sum) / 4.0;
-          strength = (strength < 0.0) ? 0.0 : ((strength > 1.0) ? 1.0 : strength);
-        }
-        o6[4] = strength;
-        o6[5] = contrast;
-      }
-      __syncthreads();
     }
   }
+  double contrast = 0.0;
+  if (tid == 0) {
+    const double total_mean = mean_of(total_sum, T, c.S[0]);
+    // Mean of a single-element list is the element; psum / vsum hold exactly that element then
+    const double peak_mean = mean_of(psum, np, psum);
+    const double valley_mean = mean_of(vsum, np, vsum) + 0.0001;
+    if (peak_mean != 0.0) contrast = -1.0 * pow(peak_mean / valley_mean, 1.0 / log(total_mean + 0.0001));
+  }
+  return contrast;
+}
 
-  // the last analysed frame above the threshold travels to rhythm_final_kernel in the slot of the final results
-  if (tid == 0) out[12 + (blockIdx.x & 1)] = (double)last_loud[blockIdx.x & 1];
+// the function's six results, by one thread: OnsetCount, the tempo and confidence of its chain, RhythmFrequencyMean
+// (RT.cpp:288-289), RhythmStrength (RT.cpp:316-318), the contrast
+__device__ __forceinline__ void post_results(double* six, int T, int count, double tempo, double confidence, int n_peaks,
+                                             double peak_sum, double contrast) {
+  six[0] = (double)count;
+  six[1] = tempo;
+  six[2] = confidence;
+  six[3] = (double)n_peaks / (double)T * (double)kRtHop / (double)512;
+  double strength = 0.0;
+  if (n_peaks) {
+    strength = mean_of(peak_sum, n_peaks, peak_sum) / 4.0;
+    strength = (strength < 0.0) ? 0.0 : ((strength > 1.0) ? 1.0 : strength);
+  }
+  six[4] = strength;
+  six[5] = contrast;
+}
+
+// One workgroup per (file, onset function): the two chains of a file are independent up to the final tempo, which
+// rhythm_final_kernel derives from both (a lone long file is latency-bound: two workgroups halve its time).
+// row: [0..5] the complex function's results, [6..11] the power function's, [12 + type] the last analysed frame above
+// MPeakThreshold, which travels to rhythm_final_kernel in the slot of its final results.
+__global__ __launch_bounds__(256, kPostWavesPerSimd) void rhythm_post_kernel(RhythmArgs a) {
+  __shared__ PostLds lds;
+  extern __shared__ double s_series[];     // the sharpened onsets of the file, de-interleaved by 4, when they fit
+  const RhythmFile f = a.files[blockIdx.x >> 1];
+  const int T = f.frames, tid = threadIdx.x, type = blockIdx.x & 1;
+  double* row = a.scalars + (int64_t)(blockIdx.x >> 1) * 14;
+  if (T <= 0) {
+    if (tid < 6) row[6 * type + tid] = 0.0;
+    if (tid == 0) row[12 + type] = 0.0;
+    return;
+  }
+  const int64_t tot = a.total_frames;
+  const PostChain c = {T, type, a.scratch + (int64_t)(0 + type) * tot + f.frame0, a.scratch + (int64_t)(2 + type) * tot + f.frame0,
+                       a.scratch + (int64_t)(4 + type) * tot + f.frame0, a.scratch + (int64_t)(6 + type) * tot + f.frame0};
+  if (tid == 0) { lds.carried_post = 0.f; lds.next_allowed = lds.onset_count = lds.peak_count = lds.last_loud = 0; }   // mOdfvalpost, mGapLeft
+  __syncthreads();
+  const int count = detect_onsets(a, f, c, lds);
+  canny_sharpen(a, c, lds);
+  double tempo = 0.0, confidence = 0.0;
+  if (count >= 4) track_beats(a, c, lds, s_series, tempo, confidence);
+  int n_peaks, last_loud;
+  window_peaks(c, lds, n_peaks, last_loud);
+  const double peak_sum = serial_sum(T, [&](int i) { return (c.S[i] > 0.1 && c.W[i] != 0.0) ? c.S[i] : 0.0; }, lds.stage, &lds.sum);
+  const double total_sum = serial_sum(T, [&](int i) { return c.S[i]; }, lds.stage, &lds.sum);
+  // CalculateRhythmContrast (RT.cpp:325-412): threshold = sorted[(int)(0.85 (T - 1))]
+  const double threshold = order_statistic(c.S, T, (int)(85.0 / 100.0 * (T - 1)), lds);
+  const double contrast = valley_walk(c, threshold, total_sum, lds);
+  if (tid == 0) {
+    post_results(row + 6 * type, T, count, tempo, confidence, n_peaks, peak_sum, contrast);
+    row[12 + type] = (double)last_loud;
+  }
 }
 
 // ---- final tempo: CalculateTempoWithHeuristics on the more confident function (SampleAnalyser.cpp:1029-1048, RT.cpp:238-325);
 //      one thread per file, after both chains of the file ----
+
+// GuessNumberOfBeatsFromDuration(80, 180, duration), RT.cpp:434-486
+__device__ __forceinline__ double guess_beats_from_duration(double duration) {
+  const double max_beat = 60.0 / 80.0, max_bar = 4.0 * max_beat;
+  double beats = 0.0;
+  if (duration < max_beat) beats = 0.0;
+  else if (duration < max_bar) {
+    beats = 4.0;
+    for (int divider = 2; divider >= 1; divider /= 2) {
+      if (duration < ((double)4 / (double)divider) * max_beat) { beats = 4.0 / (double)divider; break; }
+    }
+  } else {
+    for (int bars = 1; bars <= 8; bars *= 2) {
+      const double nb = 4.0 * bars;
+      if (duration / nb < max_beat) { beats = nb; break; }
+    }
+  }
+  return beats;
+}
+
+// OnsetMatchConfidence, RT.cpp:490-540: the share of the 2 x beats half-beat positions of a tempo `bpm`, counted from
+// offset_s, that have a raw onset of the function at or above its threshold nearby
+__device__ __forceinline__ double onset_match_confidence(const double* raw, int T, int type, int rate, double offset_s, double beats,
+                                                         double bpm) {
+  const float ms = (float)(offset_s * 1000);
+  const float fv = (float)rate / 1000.0f * ms;                       // MsToSamples, AudioMath.inl:127-130
+  const int offset_samples = (int)(fv + (signbit(fv) ? -0.5f : 0.5f));
+  const double spb = 60.0 / bpm * (unsigned)rate;
+  const int range = (int)((unsigned)(int)(spb / 32) / (unsigned)kRtHop);
+  const double thr = (type == 0) ? 0.2 : 0.8;
+  double strength = 0;
+  for (int i = 0; i < beats * 2; ++i) {
+    const int st = (int)(i * spb / 2.0) + offset_samples;
+    const int idx = (st + kRtHop / 2) / kRtHop;
+    double peak = 0.0;
+    for (int j = idx - range; j < idx + range; ++j)
+      if (j >= 0 && j < T) peak = (peak > raw[j]) ? peak : raw[j];
+    if (peak >= thr) strength += 1.0;
+  }
+  const double r = strength / (beats * 2) * 2.0;
+  return (1.0 < r) ? 1.0 : r;
+}
+
 __global__ __launch_bounds__(256) void rhythm_final_kernel(RhythmArgs a) {
   const int file = blockIdx.x * blockDim.x + threadIdx.x;
   if (file >= a.n_files) return;
@@ -922,86 +1042,59 @@ __global__ __launch_bounds__(256) void rhythm_final_kernel(RhythmArgs a) {
   const int T = f.frames;
   double* out = a.scalars + (int64_t)file * 14;
   if (T <= 0) { out[12] = 0.0; out[13] = 0.0; return; }
-  const int64_t tot = a.total_frames;
   const int rate = a.sample_rate;
   const double tempo[2] = {out[1], out[7]}, conf[2] = {out[2], out[8]};
   const int last_loud[2] = {(int)out[12], (int)out[13]};
-  {
-    const int type = (conf[1] > conf[0]) ? 1 : 0;
-    const double* raw = a.scratch + (int64_t)(0 + type) * tot + f.frame0;
-    double t_out = 0.0, c_out = 0.0;
-    if (tempo[type] != 0) {
-      double tp = tempo[type];
-      c_out = conf[type];
-      const double samples_per_beat = 60.0 / tp * (unsigned)rate;
-      const unsigned n_samples = (unsigned)last_loud[type] * (unsigned)kRtHop;
-      if ((double)n_samples < samples_per_beat * 3) {
-        c_out = 0.0;
-        tp = 0.0;
-      } else {
-        // GuessNumberOfBeatsFromDuration(80, 180, duration), RT.cpp:434-486
-        const double duration = f.duration_s, max_beat = 60.0 / 80.0, max_bar = 4.0 * max_beat;
-        double beats = 0.0;
-        if (duration < max_beat) beats = 0.0;
-        else if (duration < max_bar) {
-          beats = 4.0;
-          for (int divider = 2; divider >= 1; divider /= 2) {
-            if (duration < ((double)4 / (double)divider) * max_beat) { beats = 4.0 / (double)divider; break; }
-          }
-        } else {
-          for (int bars = 1; bars <= 8; bars *= 2) {
-            const double nb = 4.0 * bars;
-            if (duration / nb < max_beat) { beats = nb; break; }
-          }
-        }
-        if (beats >= 4 && beats <= 16) {
-          const double guessed = beats / (duration / 60);
-          const double delay = (double)((float)(kRtHop / 2) / ((float)rate / 1000.0f)) / 1000.0;   // SamplesToMs, AudioMath.inl:134-137
-          // OnsetMatchConfidence, RT.cpp:490-540
-          const float ms = (float)((f.offset_s + delay) * 1000);
-          const float fv = (float)rate / 1000.0f * ms;                       // MsToSamples, AudioMath.inl:127-130
-          const int offset_samples = (int)(fv + (signbit(fv) ? -0.5f : 0.5f));
-          const double spb = 60.0 / guessed * (unsigned)rate;
-          const int range = (int)((unsigned)(int)(spb / 32) / (unsigned)kRtHop);
-          const double thr = (type == 0) ? 0.2 : 0.8;
-          double strength = 0;
-          for (int i = 0; i < beats * 2; ++i) {
-            const int st = (int)(i * spb / 2.0) + offset_samples;
-            const int idx = (st + kRtHop / 2) / kRtHop;
-            double peak = 0.0;
-            for (int j = idx - range; j < idx + range; ++j)
-              if (j >= 0 && j < T) peak = (peak > raw[j]) ? peak : raw[j];
-            if (peak >= thr) strength += 1.0;
-          }
-          const double r = strength / (beats * 2) * 2.0;
-          const double g = (1.0 < r) ? 1.0 : r;
-          if ((g > 0.5) || (c_out < 0.1 && g > 0.1) || (c_out < 0.5 && fabs(guessed - tp) < 10)) {
-            tp = guessed;
-            c_out = (0.5 > g) ? 0.5 : g;
-          }
+  const int type = (conf[1] > conf[0]) ? 1 : 0;
+  const double* raw = a.scratch + (int64_t)(0 + type) * a.total_frames + f.frame0;
+  double t_out = 0.0, c_out = 0.0;
+  if (tempo[type] != 0) {
+    double tp = tempo[type];
+    c_out = conf[type];
+    const double samples_per_beat = 60.0 / tp * (unsigned)rate;
+    const unsigned n_samples = (unsigned)last_loud[type] * (unsigned)kRtHop;
+    if ((double)n_samples < samples_per_beat * 3) {
+      c_out = 0.0;
+      tp = 0.0;
+    } else {
+      const double duration = f.duration_s;
+      const double beats = guess_beats_from_duration(duration);
+      if (beats >= 4 && beats <= 16) {
+        const double guessed = beats / (duration / 60);
+        const double delay = (double)((float)(kRtHop / 2) / ((float)rate / 1000.0f)) / 1000.0;   // SamplesToMs, AudioMath.inl:134-137
+        const double g = onset_match_confidence(raw, T, type, rate, f.offset_s + delay, beats, guessed);
+        if ((g > 0.5) || (c_out < 0.1 && g > 0.1) || (c_out < 0.5 && fabs(guessed - tp) < 10)) {
+          tp = guessed;
+          c_out = (0.5 > g) ? 0.5 : g;
         }
       }
-      t_out = tp;
     }
-    out[12] = t_out;
-    out[13] = c_out;
+    t_out = tp;
   }
+  out[12] = t_out;
+  out[13] = c_out;
 }
 
 }  // namespace
+
+using OnsetKernel = void (*)(RhythmArgs);
+// the <PCM, SCALED> instantiation of a kernel template for the arena's sample type
+static OnsetKernel for_pcm(int pcm_dtype, OnsetKernel f64, OnsetKernel scaled_f32, OnsetKernel f32) {
+  return (pcm_dtype == kPcmF64) ? f64 : ((pcm_dtype == kPcmScaledF32) ? scaled_f32 : f32);
+}
 
 hipError_t launch_rhythm(const RhythmArgs& a, hipStream_t stream) {
   if (a.n_files <= 0) return hipSuccess;
   if (a.total_frames > 0) {
     if (a.n_long < a.n_files) {     // (every file long: nothing for the one-workgroup-per-file kernel)
-      if (a.pcm_dtype == kPcmF64) hipLaunchKernelGGL((onset_function_kernel<double, false>), dim3(a.n_files), dim3(256), 0, stream, a);
-      else if (a.pcm_dtype == kPcmScaledF32) hipLaunchKernelGGL((onset_function_kernel<float, true>), dim3(a.n_files), dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((onset_function_kernel<float, false>), dim3(a.n_files), dim3(256), 0, stream, a);
+      const OnsetKernel k = for_pcm(a.pcm_dtype, onset_function_kernel<double, false>, onset_function_kernel<float, true>,
+                                    onset_function_kernel<float, false>);
+      hipLaunchKernelGGL(k, dim3(a.n_files), dim3(256), 0, stream, a);
     }
     if (a.n_long > 0) {
-      if (a.pcm_dtype == kPcmF64) hipLaunchKernelGGL((onset_polar_kernel<double, false>), dim3(a.long_rounds), dim3(256), 0, stream, a);
-      else if (a.pcm_dtype == kPcmScaledF32) hipLaunchKernelGGL((onset_polar_kernel<float, true>), dim3(a.long_rounds), dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((onset_polar_kernel<float, false>), dim3(a.long_rounds), dim3(256), 0, stream, a);
+      const OnsetKernel k = for_pcm(a.pcm_dtype, onset_polar_kernel<double, false>, onset_polar_kernel<float, true>,
+                                    onset_polar_kernel<float, false>);
+      hipLaunchKernelGGL(k, dim3(a.long_rounds), dim3(256), 0, stream, a);
       hipLaunchKernelGGL(onset_follow_kernel, dim3(a.n_long), dim3(256), 0, stream, a);
       hipLaunchKernelGGL(onset_terms_kernel, dim3(a.long_rounds), dim3(256), 0, stream, a);
     }
@@ -1014,7 +1107,7 @@ hipError_t launch_rhythm(const RhythmArgs& a, hipStream_t stream) {
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 16 || !attribute_set[dev]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rhythm_post_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(kMaxLdsFrames * sizeof(double)));
+                                       (int)(kRhythmLdsFrames * sizeof(double)));
     if (e != hipSuccess) return e;
     if (dev >= 0 && dev < 16) attribute_set[dev] = true;
   }
