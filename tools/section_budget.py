@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-section instruction budget of a kernel's frame loop: a copy of the kernel's source gets a scheduling barrier and an
 assembly comment at every section boundary, is compiled to ISA (hipcc -S --cuda-device-only), and the instructions between
-the markers are counted by kind.  (The scheduler still moves some work across the markers.)
+the markers are counted by kind.  (The scheduler still moves some work across the markers.)  The band kernel's sections are
+its stages: a marker stands in front of the kernel's call of each.
 
 usage: tools/section_budget.py bands|pitch"""
 import collections
@@ -11,26 +12,22 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "afec_amd", "csrc")
+
+
+def at_call(stage):
+    """marker in front of the kernel's first statement that calls the stage, named as the stage"""
+    return (re.compile(r"^.*\b%s\(.*$" % stage, re.M), stage, True)
+
+
 KERNELS = {
     # name: (source, start of the kernel in the source (markers are placed behind it), mangled-name regex, markers);
-    # marker = (text to find, section name, before?)
-    "bands": ("afx_bands.hip", "void bands_kernel(const BandArgs a)", r"_ZN3afx12_GLOBAL__N_112bands_kernelILi15EEEvNS_8BandArgsE", [
-        ("    const int64_t f = (int64_t)ch.frame0 + fi;", "top", False),
-        ("    // ---- spectrum bands 0..25 for the half-wave frame kernel", "spectrum", True),
-        ("    // ---- the raw sums of the spectral statistics over bins 1..738", "stats", True),
-        ("      const double total = read_lane<0>(red);", "rolloff", True),
-        ("    // ---- spectral_flux: Pearson r with the previous frame", "flux", True),
-        ("    // ---- masked per-band sums: lane L ends up with band", "bandsums3", True),
-        ("    double lg[8];", "logs", True),
-        ("    const double bmax = band_max(", "bmax", True),
-        ("    // ---- complexity: strict local maxima above", "peaks", True),
-        ("    // ---- contrast: sort (band, value) keys", "sortprep", True),
-        ("    sort_level<256>(key, lane_v);", "sort", True),
-        ("    sort_level<256>(key, lane_v);", "cuts", False),
-        ("    double vsum, psum;", "vpsum", True),
-        ("    // cuts inside a tie class: exact resolution", "ties", True),
-        ("    // ---- park the frame", "park (closed forms: once per four frames)", True),
-        ("    // this frame is the next one", "tail", True)]),
+    # marker = (text to find or, from at_call(), a pattern of the line to find, section name, before?)
+    "bands": ("afx_bands.hip", "void bands_kernel(const BandArgs a)", r"_ZN3afx12_GLOBAL__N_112bands_kernelILi15EEEvNS_8BandArgsE",
+              [at_call(stage) for stage in (
+                  "chunk_prologue", "spectrum_bands", "spectral_sums", "rolloff_count", "whole_range_sum", "flux_only_frame", "band_sum",
+                  "band_logs", "band_max", "count_local_maxima", "sort_blocks", "two_run_cuts", "cut_keys_and_ties", "cut_sums",
+                  "park_frame", "finish_group")] +
+              [("        // this frame is the next one", "tail", True)]),
     "pitch": ("afx_time.hip", "void pitch_kernel(const TimeArgs a)", r"_ZN3afx12_GLOBAL__N_112pitch_kernelIfLb1EEEvNS_8TimeArgsE", [
         ("      cx<double> zn[16];", "convert + prefetch", True),
         ("      fft(zn, c);", "forward transform", True),
@@ -53,6 +50,10 @@ def main():
     at = text.index(start)
     head, body = text[:at], text[at:]
     for find, section, before in markers:
+        if not isinstance(find, str):
+            m = find.search(body)
+            assert m, find.pattern
+            find = m.group(0)
         assert find in body, find
         mark = '__builtin_amdgcn_sched_barrier(0); asm volatile("; M_%s");\n' % re.sub(r"\W+", "_", section)
         body = body.replace(find, (mark + find) if before else (find + "\n" + mark), 1)
