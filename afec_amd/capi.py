@@ -99,6 +99,9 @@ EXPORTS = [
     "afx_batch_high_level_row_capacity", "afx_batch_fetch_high_level_row", "afx_format_class_json",
 ]
 RAW_I16, RAW_I24, RAW_F32, RAW_I32, RAW_F64 = 0, 1, 2, 3, 4
+RAW_I16_BE, RAW_I24_BE, RAW_F32_BE, RAW_I32_BE, RAW_F64_BE = 5, 6, 7, 8, 9   # the same with Motorola byte order (AIFF)
+_RAW_BYTES = {RAW_I16: 2, RAW_I24: 3, RAW_F32: 4, RAW_I32: 4, RAW_F64: 8,
+              RAW_I16_BE: 2, RAW_I24_BE: 3, RAW_F32_BE: 4, RAW_I32_BE: 4, RAW_F64_BE: 8}
 
 # afx_out fields: name -> width per frame, in declaration order
 OUT_FIELDS = [
@@ -627,7 +630,13 @@ class Plan:
             data, channels = item[0], int(item[1])
             rate = int(item[2]) if len(item) > 2 else 0
             data = np.ascontiguousarray(np.asarray(data).reshape(-1))
-            if data.dtype == np.int16:
+            if len(item) > 3 and item[3] is not None:
+                # (array, channels, sample_rate, RAW_* code): the array's bytes as they are, in the stated format --
+                # how the big-endian formats are handed over (a NumPy dtype does not say "AIFF payload")
+                fmt = int(item[3])
+                data = data.view(np.uint8)
+                frames = data.size // (_RAW_BYTES.get(fmt, 1) * max(channels, 1))
+            elif data.dtype == np.int16:
                 fmt, frames = RAW_I16, data.size // max(channels, 1)
             elif data.dtype == np.float32:
                 fmt, frames = RAW_F32, data.size // max(channels, 1)

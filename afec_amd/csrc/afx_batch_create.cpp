@@ -10,8 +10,14 @@
 #include <cstring>
 
 #include "afx_host.h"
+#include "rawpcm/afx_rawpcm.h"
 
 namespace afx {
+// A weak reference: the library defines the launcher (rawpcm/afx_rawpcm.hip); the mock builds of tests/sanitize link this
+// file from a fixed list without it, find it null and refuse big-endian buffers
+extern hipError_t launch_raw_native(unsigned char* raw, const RawNativeFile* files, int n_files, int64_t n_tiles, hipStream_t stream)
+    __attribute__((weak));
+
 namespace host {
 
 namespace {
@@ -40,7 +46,23 @@ int raw_bytes_per_sample(int format) {
     case AFX_RAW_I24: return 3;
     case AFX_RAW_F32: case AFX_RAW_I32: return 4;
     case AFX_RAW_F64: return 8;
+    case AFX_RAW_I16_BE: return 2;
+    case AFX_RAW_I24_BE: return 3;
+    case AFX_RAW_F32_BE: case AFX_RAW_I32_BE: return 4;
+    case AFX_RAW_F64_BE: return 8;
     default: return 0;
+  }
+}
+
+// the native format of the same width and meaning (raw_native_kernel has turned the bytes round); -1 for a native format
+int native_twin(int format) {
+  switch (format) {
+    case AFX_RAW_I16_BE: return AFX_RAW_I16;
+    case AFX_RAW_I24_BE: return AFX_RAW_I24;
+    case AFX_RAW_F32_BE: return AFX_RAW_F32;
+    case AFX_RAW_I32_BE: return AFX_RAW_I32;
+    case AFX_RAW_F64_BE: return AFX_RAW_F64;
+    default: return -1;
   }
 }
 
@@ -129,6 +151,8 @@ void lay_out_raw_arena(RawBatch& r) {
     const bool good = bps && f.data && f.n_frames > 0 && f.n_frames < 0x7FFFFFFF && f.channels >= 1 && f.channels <= 8 && f.sample_rate >= 0;
     r.files[(size_t)i] = LoadFile{0, 0, 0, 0};
     if (!good) { r.status[(size_t)i] = AFX_ERR_BAD_BUFFER; continue; }
+    // a build without the byte-order kernel (the mock device) refuses a big-endian file like any other it cannot take
+    if (native_twin(f.format) >= 0 && !launch_raw_native) { r.status[(size_t)i] = AFX_ERR_UNSUPPORTED; continue; }
     r.files[(size_t)i] = LoadFile{r.raw_bytes, f.n_frames, f.channels, f.format};
     r.raw_bytes += ((int64_t)f.n_frames * f.channels * bps + 15) & ~(int64_t)15;
   }
@@ -214,22 +238,80 @@ hipError_t upload_raw(RawBatch& r, const char** what) {
   return hipSuccess;
 }
 
-// upload -> (conversion) -> the scan kernels (peak, rms, first / last sample above the floor) -> results on the host
+// Big-endian files (AFX_RAW_*_BE) become native in place in the raw arena, one launch for the batch
+// (rawpcm/afx_rawpcm.hip).  This is the host's half, before anything is enqueued: the kernel's table from the files as
+// the caller described them, and then the file and conversion tables name the native twin, which is all afx_resample.hip
+// and afx_load.hip know.  It runs before plan_converted_files() below puts kRawMonoFloat into the file table: that
+// internal value equals AFX_RAW_I16_BE (afx_internal.h), and native_twin() must never see it.
+static_assert(kRawMonoFloat == AFX_RAW_I16_BE, "the two share a value: keep name_native_twins() in front of plan_converted_files()");
+hipError_t name_native_twins(RawBatch& r, std::vector<RawNativeFile>& be, int64_t& n_tiles) {
+  n_tiles = 0;
+  for (int i = 0; i < r.n_bufs; ++i) {
+    LoadFile& f = r.files[(size_t)i];
+    if (r.status[(size_t)i] != AFX_OK || native_twin(f.format) < 0) continue;
+    const int bps = raw_bytes_per_sample(f.format);
+    const int64_t bytes = f.n_frames * f.channels * bps;
+    if (n_tiles > 0x7FFFFFFF - raw_native_tiles(bytes)) return hipErrorInvalidValue;
+    be.push_back(RawNativeFile{f.raw_off, bytes, bps, (int32_t)n_tiles});
+    n_tiles += raw_native_tiles(bytes);
+    f.format = native_twin(f.format);
+  }
+  if (!be.empty())
+    for (ResampleFile& c : r.conv)
+      if (native_twin(c.format) >= 0) c.format = native_twin(c.format);
+  return hipSuccess;
+}
+
+// what the LoadSample kernels read of a converted file: its converted samples, a mono file of "16-bit floats".  `files`
+// is r.files once the PCM has gone up (upload_raw lays the arena out by the entries as they were), or a copy on its way up.
+void plan_converted_files(const RawBatch& r, LoadFile* files) {
+  for (size_t k = 0; k < r.conv.size(); ++k)
+    files[(size_t)r.conv_buf[k]] = LoadFile{r.conv[k].out_off, r.conv[k].n_out, 1, kRawMonoFloat};
+}
+
+// upload -> (byte order) -> (conversion) -> the scan kernels (peak, rms, first / last sample above the floor) -> results on the host
 hipError_t stage_and_scan(RawBatch& r, const char** what) {
   afx_plan* plan = r.plan;
   Workspace* ws = r.ws;
   hipStream_t s = ws->stream;
   const int n_bufs = r.n_bufs;
   hipError_t e;
+  std::vector<RawNativeFile> be;
+  int64_t be_tiles = 0;
+  *what = "raw_native";
+  if ((e = name_native_twins(r, be, be_tiles)) != hipSuccess) return e;
+  // The page-locked block and its device twin: the file table, behind it (a batch with big-endian files only) the byte-order
+  // kernel's table, then the scan results on their way down.  A batch without such a file has the layout and makes the
+  // calls it always did.
+  const size_t files_bytes = r.files.size() * sizeof(LoadFile), scan_bytes = r.scan.size() * sizeof(LoadScan);
+  const size_t be_off = (files_bytes + 63) & ~(size_t)63, be_bytes = be.size() * sizeof(RawNativeFile);
+  const size_t tables_bytes = be.empty() ? files_bytes : be_off + be_bytes;
+  const size_t scan_off = (tables_bytes + 63) & ~(size_t)63;
   *what = "hipMalloc(raw staging)";
   if ((e = ws_reserve(plan, ws->raw, (size_t)(r.raw_bytes + r.conv_bytes) + 16)) != hipSuccess) return e;
-  if ((e = ws_reserve(plan, ws->files, r.files.size() * sizeof(LoadFile))) != hipSuccess) return e;
+  if ((e = ws_reserve(plan, ws->files, tables_bytes)) != hipSuccess) return e;
   if ((e = ws_reserve(plan, ws->scan, r.scan.size() * sizeof(LoadScan))) != hipSuccess) return e;
   if ((e = ws_reserve(plan, ws->partial, (size_t)n_bufs * load_scan_blocks_per_file(n_bufs) * 16)) != hipSuccess) return e;
   r.d_raw = (unsigned char*)ws->raw.p;
   r.d_files = (LoadFile*)ws->files.p;
   LoadScan* d_scan = (LoadScan*)ws->scan.p;
+  if (!be.empty()) {
+    // Both tables in ONE copy, enqueued before the PCM goes up: the file table is known on the host already (the
+    // converted files' entries included), so nothing but the kernel's launch stands between the upload and the scan.
+    *what = "raw_native";
+    if ((e = ws_pin_reserve(ws, scan_off + scan_bytes)) != hipSuccess) return e;
+    std::memcpy(ws->h_pin, r.files.data(), files_bytes);
+    plan_converted_files(r, (LoadFile*)ws->h_pin);
+    std::memcpy((unsigned char*)ws->h_pin + be_off, be.data(), be_bytes);
+    if ((e = hipMemcpyAsync(r.d_files, ws->h_pin, tables_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  }
   if ((e = upload_raw(r, what)) != hipSuccess) return e;
+  // behind the upload as load_scan is: upload_through_plan returns when its transfer has landed (the host waits,
+  // afx_workspace.cpp), the per-file copies are on `s` themselves
+  if (!be.empty()) {
+    *what = "raw_native";
+    if ((e = launch_raw_native(r.d_raw, (const RawNativeFile*)((const unsigned char*)ws->files.p + be_off), (int)be.size(), be_tiles, s)) != hipSuccess) return e;
+  }
   if (!r.conv.empty()) {
     *what = "resample";
     if ((e = resample_filter_table(plan)) != hipSuccess) return e;
@@ -239,17 +321,16 @@ hipError_t stage_and_scan(RawBatch& r, const char** what) {
     if ((e = hipMemcpyAsync(ws->rs_files.p, r.conv.data(), r.conv.size() * sizeof(ResampleFile), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
     if ((e = launch_resample(r.d_raw, (const ResampleFile*)ws->rs_files.p, (int)r.conv.size(), r.conv_blocks, r.conv_max_in,
                              (ResampleGroup*)ws->rs_groups.p, plan->dev.rs_filter, s)) != hipSuccess) return e;
-    for (size_t k = 0; k < r.conv.size(); ++k)
-      r.files[(size_t)r.conv_buf[k]] = LoadFile{r.conv[k].out_off, r.conv[k].n_out, 1, kRawMonoFloat};
+    plan_converted_files(r, r.files.data());
   }
   *what = "load_scan";
   // the file table up and the scan results down through the workspace's page-locked block (pageable copies are staged
   // by the runtime on this thread and complete through its event thread: host CPU a crawl's workers do not have to spend)
-  const size_t files_bytes = r.files.size() * sizeof(LoadFile), scan_bytes = r.scan.size() * sizeof(LoadScan);
-  const size_t scan_off = (files_bytes + 63) & ~(size_t)63;
-  if ((e = ws_pin_reserve(ws, scan_off + scan_bytes)) != hipSuccess) return e;
-  std::memcpy(ws->h_pin, r.files.data(), files_bytes);
-  if ((e = hipMemcpyAsync(r.d_files, ws->h_pin, files_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  if (be.empty()) {
+    if ((e = ws_pin_reserve(ws, scan_off + scan_bytes)) != hipSuccess) return e;
+    std::memcpy(ws->h_pin, r.files.data(), files_bytes);
+    if ((e = hipMemcpyAsync(r.d_files, ws->h_pin, files_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  }
   // -48 dB of full scale (MSilenceThresholdDb, SampleAnalyser.cpp:51, 648-649)
   const double silence_floor = 32768.0 * std::exp(-48.0 * (std::log(10.0) / 20.0));
   if ((e = launch_load_scan(r.d_raw, r.d_files, n_bufs, silence_floor, ws->partial.p, d_scan, s)) != hipSuccess) return e;

@@ -318,7 +318,7 @@ struct LoadFile {
   int64_t raw_off;   // byte offset of the interleaved PCM in the raw arena
   int64_t n_frames;  // sample frames
   int32_t channels;
-  int32_t format;    // AFX_RAW_*
+  int32_t format;    // a native AFX_RAW_* (0..4; a big-endian file has been made native by then, rawpcm/afx_rawpcm.hip), or kRawMonoFloat
 };
 struct LoadScan {    // per file, produced by the scan kernels
   double sum_sq;         // sum (x / 32768)^2 of the mono mix
@@ -335,7 +335,10 @@ struct LoadPlace {   // per file, where the normalised samples go
   int64_t start_pad; // zeros in front (StartFrameOffset)
   double scaling;    // FinalScaling
 };
-constexpr int kRawMonoFloat = 5;   // LoadFile::format of a converted file: mono floats already in the "16-bit float" range
+// LoadFile::format of a converted file: mono floats already in the "16-bit float" range.  Internal to the device tables; its
+// value is also the public AFX_RAW_I16_BE's, which never reaches a device table (afx_batch_create.cpp: name_native_twins()
+// runs before this value is written, and a static_assert there names the coincidence)
+constexpr int kRawMonoFloat = 5;
 int load_scan_blocks_per_file(int n_files);      // partial_scratch holds n_files x this x 16 bytes
 hipError_t launch_load_scan(const unsigned char* raw, const LoadFile* files, int n_files, double silence_floor,
                             void* partial_scratch, LoadScan* scan, hipStream_t stream);

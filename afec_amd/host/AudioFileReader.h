@@ -1,0 +1,36 @@
+// afec_amd/host/AudioFileReader.h -- what the crawler needs of a container reader that is not TWaveFile, as an interface
+// that lives in this header alone.  afec_amd/host/Crawler.cpp is also linked into the mock-device builds of tests/sanitize
+// from a fixed list of files that cannot include AifFile.cpp: it reaches TAifFile through this interface and the weak factory
+// below, and so names no symbol of AifFile.cpp -- not even its type information, which the sanitizer builds' checks of
+// virtual calls would otherwise ask for.
+#pragma once
+
+#include <cstdint>
+#include <string>
+
+#include "SampleAnalyser.h"
+
+namespace afec {
+
+class TAudioFileReader {
+public:
+  virtual ~TAudioFileReader() = default;
+  // as TWaveFile's functions of the same names
+  virtual void OpenForRead(const std::string& FileName) = 0;
+  virtual void OpenForRead(const void* pImage, size_t SizeInBytes, const std::string& Name) = 0;
+  virtual void Close() = 0;
+  virtual int NumChannels() const = 0;
+  virtual int SamplingRate() const = 0;
+  virtual int BitsPerSample() const = 0;
+  virtual int SampleType() const = 0;
+  virtual int64_t NumSamples() const = 0;
+  virtual size_t FileSizeInBytes() const = 0;
+  virtual TDecodedSample DescribeSample() const = 0;
+  virtual size_t SampleDataBytes() const = 0;
+  virtual void ReadSampleData(void* pDst) const = 0;
+};
+
+// a new TAifFile (AifFile.cpp); the caller deletes it.  Crawler.cpp refers to it weakly and checks for null.
+TAudioFileReader* NewAifFile();
+
+}  // namespace afec

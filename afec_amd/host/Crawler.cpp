@@ -2,6 +2,7 @@
 #include "Crawler.h"
 
 #include <atomic>
+#include <cctype>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -19,8 +20,26 @@
 #include "../../include/afx.h"
 #include "SqlitePool.h"
 #include "WaveFile.h"
+#include "AudioFileReader.h"
 
 namespace afec {
+
+// A weak reference: libafx_host.so holds AifFile.cpp; the mock-device builds of tests/sanitize link this file from a fixed
+// list without it, find the factory null and fail an AIFF like any other file they cannot read (AudioFileReader.h)
+TAudioFileReader* NewAifFile() __attribute__((weak));
+
+// TAifFile::SSupportedExtensions through gFileMatchesExtension (Directory.cpp:581-615): the end of the name, compared
+// without regard to case
+const char* AifFileTypeOf(const std::string& FileName) {
+  for (const char* pType : {"aiff", "aifc", "aif", "snd"}) {
+    const size_t n = std::strlen(pType) + 1;   // with the dot
+    if (FileName.size() < n || FileName[FileName.size() - n] != '.') continue;
+    bool Same = true;
+    for (size_t k = 0; k + 1 < n && Same; ++k) Same = std::tolower((unsigned char)FileName[FileName.size() - n + 1 + k]) == pType[k];
+    if (Same) return pType;
+  }
+  return nullptr;
+}
 
 namespace {
 
@@ -124,7 +143,12 @@ int64_t FileBytes(const TCrawlFile& f) {
 }
 
 int64_t BytesPerSample(int Format) {
-  return Format == AFX_RAW_I16 ? 2 : (Format == AFX_RAW_I24 ? 3 : (Format == AFX_RAW_F64 ? 8 : 4));
+  switch (Format) {
+    case AFX_RAW_I16: case AFX_RAW_I16_BE: return 2;
+    case AFX_RAW_I24: case AFX_RAW_I24_BE: return 3;
+    case AFX_RAW_F64: case AFX_RAW_F64_BE: return 8;
+    default: return 4;
+  }
 }
 
 // a digest of everything the device returned for file k of a batch (TCrawlOptions::mRowDigests); never 0, which says
@@ -288,32 +312,42 @@ private:
     size_t Bytes = 0;
     Staging.Reserve((size_t)Work.mFileBytes + 16 * n + 64);
     TWaveFile Wave;
-    for (size_t i = 0; i < n; ++i) {
+    std::unique_ptr<TAudioFileReader> pAif;   // made by the first AIFF of the batch
+    // the same steps for either reader
+    auto Stage = [&](auto& File, const char* pFileType, size_t i) {
       try {
         const TCrawlFile& f = *Done.mFiles[i];
-        if (f.mpImage) Wave.OpenForRead(f.mpImage, f.mImageSize, f.mFileName);
-        else Wave.OpenForRead(f.mFileName);
-        if (!mOptions.mResample && Wave.SamplingRate() != mOptions.mSampleRate) { Done.mSkipped[i] = 1; Wave.Close(); continue; }
-        TDecodedSample s = Wave.DescribeSample();
-        const size_t Size = Wave.SampleDataBytes();
+        if (f.mpImage) File.OpenForRead(f.mpImage, f.mImageSize, f.mFileName);
+        else File.OpenForRead(f.mFileName);
+        if (!mOptions.mResample && File.SamplingRate() != mOptions.mSampleRate) { Done.mSkipped[i] = 1; File.Close(); return; }
+        TDecodedSample s = File.DescribeSample();
+        const size_t Size = File.SampleDataBytes();
         if (Bytes + Size + 64 > Staging.mBytes) Staging.Reserve(Bytes + Size + 64, Bytes);
-        Wave.ReadSampleData((char*)Staging.mp + Bytes);
-        Wave.Close();
+        File.ReadSampleData((char*)Staging.mp + Bytes);
+        File.Close();
         TFileProperties& p = Done.mProperties[i];
-        p.mFileType = "wav";
-        p.mFileSize = (int)Wave.FileSizeInBytes();
-        p.mFileLength = (double)Wave.NumSamples() / (double)Wave.SamplingRate();
-        p.mFileSampleRate = Wave.SamplingRate();
-        p.mFileChannelCount = Wave.NumChannels();
-        p.mFileBitDepth = Wave.BitsPerSample();
+        p.mFileType = pFileType;
+        p.mFileSize = (int)File.FileSizeInBytes();
+        p.mFileLength = (double)File.NumSamples() / (double)File.SamplingRate();
+        p.mFileSampleRate = File.SamplingRate();
+        p.mFileChannelCount = File.NumChannels();
+        p.mFileBitDepth = File.BitsPerSample();
         Done.mBatchIndex[i] = (int)Decoded.size();
         Decoded.push_back(s);
         Offset.push_back(Bytes);
         Bytes += (Size + 15) & ~(size_t)15;
       } catch (const TReadableException& e) {
-        Wave.Close();
+        File.Close();
         Done.mFailed[i] = std::string("Sample failed to load: ") + e.what();   // SampleAnalyser.cpp:372-387
       }
+    };
+    for (size_t i = 0; i < n; ++i) {
+      // by extension, as TAudioFile::SCreateFromFile does (AudioFile.cpp:186-234); every other name is a WAV's, as before
+      const char* pAifType = AifFileTypeOf(Done.mFiles[i]->mFileName);
+      if (!pAifType) { Stage(Wave, "wav", i); continue; }
+      if (!pAif && NewAifFile) pAif.reset(NewAifFile());
+      if (pAif) Stage(*pAif, pAifType, i);
+      else Done.mFailed[i] = "Sample failed to load: AIFF files are not supported by this build.";
     }
     for (size_t k = 0; k < Decoded.size(); ++k) Decoded[k].mpInterleavedSamples = (char*)Staging.mp + Offset[k];
     std::lock_guard<std::mutex> Lock(mStatMutex);
@@ -767,6 +801,37 @@ extern "C" int afec_crawl_wave_images_ex(const char* const* names, const void* c
 }
 
 namespace {
+// what both probes report, from either reader
+template <class TFile>
+int AudioProbe(TFile& File, int64_t* props, void* payload, int64_t payload_capacity) {
+  const afec::TDecodedSample s = File.DescribeSample();
+  const int64_t Bytes = (int64_t)File.SampleDataBytes();
+  props[0] = File.NumChannels(); props[1] = File.SamplingRate(); props[2] = File.BitsPerSample();
+  props[3] = (int64_t)File.SampleType(); props[4] = File.NumSamples(); props[5] = s.mFormat; props[6] = Bytes;
+  if (payload && Bytes <= payload_capacity) File.ReadSampleData(payload);
+  return 0;
+}
+// name: what decides the reader (and, for image == NULL, the path of a file on disk)
+int AudioProbeByName(const char* name, const void* image, int64_t size, int64_t* props, void* payload, int64_t payload_capacity,
+                     char* file_type, int32_t file_type_size, char* error, int32_t error_size) {
+  try {
+    const std::string Name = name ? name : "";
+    const char* pAifType = afec::AifFileTypeOf(Name);
+    if (file_type && file_type_size > 0) std::snprintf(file_type, (size_t)file_type_size, "%s", pAifType ? pAifType : "wav");
+    if (!pAifType) {
+      afec::TWaveFile Wave;
+      if (image) Wave.OpenForRead(image, (size_t)size, Name); else Wave.OpenForRead(Name);
+      return AudioProbe(Wave, props, payload, payload_capacity);
+    }
+    if (!afec::NewAifFile) throw afec::TReadableException("AIFF files are not supported by this build.");
+    std::unique_ptr<afec::TAudioFileReader> pAif(afec::NewAifFile());
+    if (image) pAif->OpenForRead(image, (size_t)size, Name); else pAif->OpenForRead(Name);
+    return AudioProbe(*pAif, props, payload, payload_capacity);
+  } catch (const std::exception& e) {
+    if (error && error_size > 0) std::snprintf(error, (size_t)error_size, "%s", e.what());
+    return -1;
+  }
+}
 int WaveProbe(afec::TWaveFile& Wave, int64_t* props, void* payload, int64_t payload_capacity) {
   const afec::TDecodedSample s = Wave.DescribeSample();
   const int64_t Bytes = (int64_t)Wave.SampleDataBytes();
@@ -799,6 +864,20 @@ extern "C" int afec_wave_probe_file(const char* path, int64_t* props, void* payl
     if (error && error_size > 0) std::snprintf(error, (size_t)error_size, "%s", e.what());
     return -1;
   }
+}
+
+extern "C" int afec_audio_probe(const char* name, const void* image, int64_t size, int64_t* props, void* payload,
+                                int64_t payload_capacity, char* file_type, int32_t file_type_size, char* error, int32_t error_size) {
+  if (!image) {
+    if (error && error_size > 0) std::snprintf(error, (size_t)error_size, "afec_audio_probe: no image");
+    return -1;
+  }
+  return AudioProbeByName(name, image, size, props, payload, payload_capacity, file_type, file_type_size, error, error_size);
+}
+
+extern "C" int afec_audio_probe_file(const char* path, int64_t* props, void* payload, int64_t payload_capacity, char* file_type,
+                                     int32_t file_type_size, char* error, int32_t error_size) {
+  return AudioProbeByName(path, nullptr, 0, props, payload, payload_capacity, file_type, file_type_size, error, error_size);
 }
 
 extern "C" double afec_usable_host_cpus(void) { return afec::UsableHostCpus(); }

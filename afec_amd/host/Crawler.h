@@ -216,6 +216,9 @@ TCrawlOptions CrawlOptionsFromSetters(const int32_t* devices, int32_t n_devices,
 // Crawl on the process' crawler for Options' devices and kernel layout (built on first use, kept until
 // afec_crawl_release); crawls through it run one at a time
 TCrawlStatistics CrawlOnKeptCrawler(const std::vector<TCrawlFile>& Files, const TCrawlOptions& Options);
+// "aif" / "aiff" / "aifc" / "snd" when the name ends in that extension, in any case: the file goes to TAifFile and this is
+// its file_type_S; nullptr for every other name, which goes to TWaveFile (the reference's dispatch, AudioFile.cpp:186-234)
+const char* AifFileTypeOf(const std::string& FileName);
 // the statistics in the layout afec_crawl_wave_images_ex documents; any pointer may be NULL
 void StoreCrawlStatistics(const TCrawlStatistics& s, int32_t n_files, int32_t n_devices, double* stats, double* device_stats,
                           uint64_t* row_digests, double* crawl_facts);
@@ -251,6 +254,12 @@ int afec_wave_probe(const void* image, int64_t size, int64_t* props /* [7] */, v
 // the same for a file on disk (TWaveFile::OpenForRead(FileName): head parsed, data chunk read by pread)
 int afec_wave_probe_file(const char* path, int64_t* props /* [7] */, void* payload, int64_t payload_capacity, char* error,
                          int32_t error_size);
+// afec_wave_probe behind the crawler's dispatch: `name` decides the reader (AifFileTypeOf), props is afec_wave_probe's
+// (TSampleType in TAifFile's numbering for an AIFF), file_type (NULL or file_type_size bytes) receives file_type_S
+int afec_audio_probe(const char* name, const void* image, int64_t size, int64_t* props /* [7] */, void* payload,
+                     int64_t payload_capacity, char* file_type, int32_t file_type_size, char* error, int32_t error_size);
+int afec_audio_probe_file(const char* path, int64_t* props /* [7] */, void* payload, int64_t payload_capacity, char* file_type,
+                          int32_t file_type_size, char* error, int32_t error_size);
 int afec_shard_of_file(int64_t file_index, int32_t n_devices);
 void afec_crawl_release(void);
 // ends the crawl that is running through afec_crawl_wave_images_ex early (TCrawlOptions::mpAbortRequested; the

@@ -72,7 +72,7 @@ struct TSampleDescriptors {
 // one decoded file as the reference's decoders hand it to LoadSample: interleaved PCM (SampleAnalyser.cpp:484-530)
 struct TDecodedSample {
   const void* mpInterleavedSamples;
-  int mFormat;              // AFX_RAW_I16 / AFX_RAW_I24 / AFX_RAW_F32 of include/afx.h
+  int mFormat;              // AFX_RAW_* of include/afx.h (the big-endian ones included: an AIFF's sample data)
   int mNumberOfChannels;    // 1..8
   int mSampleRate;          // 0 = the analyser's rate; other rates are converted on the GPU (SampleAnalyser.cpp:563-607)
   int64_t mNumberOfSampleFrames;

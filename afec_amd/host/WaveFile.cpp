@@ -22,6 +22,14 @@ constexpr uint16_t kWaveFormatPcm = 1, kWaveFormatIeeeFloat = 3, kWaveFormatExte
 uint16_t Read16(const unsigned char* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 uint32_t Read32(const unsigned char* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
+struct TChunk {
+  char mName[5];
+  size_t mOffset;   // of the chunk's data
+  uint32_t mSize;
+};
+
+}  // namespace
+
 // A data chunk copied out of a file image is written once and next read by the GPU's DMA engine: non-temporal
 // stores (no read-for-ownership of the destination lines, nothing of it left in the caches) -- half the CPU time
 // of memcpy for the crawler's staging copies (profiles/r03/README.md).
@@ -46,14 +54,6 @@ void CopyStreaming(void* pDst, const void* pSrc, size_t Bytes) {
   std::memcpy(d, s, Bytes);
   _mm_sfence();
 }
-
-struct TChunk {
-  char mName[5];
-  size_t mOffset;   // of the chunk's data
-  uint32_t mSize;
-};
-
-}  // namespace
 
 TWaveFile::~TWaveFile() { Close(); }
 

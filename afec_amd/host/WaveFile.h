@@ -17,6 +17,9 @@
 
 namespace afec {
 
+// the copy of a file's sample data into the caller's (page-locked) memory, shared by the readers (WaveFile.cpp)
+void CopyStreaming(void* pDst, const void* pSrc, size_t Bytes);
+
 class TWaveFile {
 public:
   // TAudioFile::TSampleType (Export/AudioFile.h) restricted to what a WAV can hold

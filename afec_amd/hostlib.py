@@ -100,6 +100,41 @@ def wave_probe_file(path):
     return d, payload[:d["payload_bytes"]].tobytes()
 
 
+_PROBE_KEYS = ["channels", "rate", "bits", "sample_type", "frames", "raw_format", "payload_bytes"]
+
+
+def _audio_probe(call, capacity):
+    props = (ctypes.c_int64 * 7)()
+    err = ctypes.create_string_buffer(256)
+    file_type = ctypes.create_string_buffer(16)
+    payload = np.zeros(capacity, dtype=np.uint8)
+    if call(props, payload.ctypes.data, payload.size, file_type, 16, err, 256) != 0:
+        raise RuntimeError(err.value.decode())
+    d = dict(zip(_PROBE_KEYS, [int(v) for v in props]))
+    d["file_type"] = file_type.value.decode()
+    return d, payload[:d["payload_bytes"]].tobytes()
+
+
+def audio_probe(name, image):
+    """wave_probe behind the crawler's dispatch by extension (afec_audio_probe): `name` decides between the WAV and the AIFF
+    reader.  -> (dict of wave_probe's properties + "file_type", payload bytes as they go to the device) or raises
+    RuntimeError with the reader's message."""
+    L = lib()
+    L.afec_audio_probe.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p,
+                                   ctypes.c_int64, ctypes.c_char_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]
+    buf = np.frombuffer(image, dtype=np.uint8) if len(image) else np.zeros(1, dtype=np.uint8)
+    return _audio_probe(lambda *rest: L.afec_audio_probe(str(name).encode(), buf.ctypes.data, len(image), *rest), 2 * len(image) + 16)
+
+
+def audio_probe_file(path):
+    """audio_probe for a file on disk (head parsed, sample data read by pread)."""
+    L = lib()
+    L.afec_audio_probe_file.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_char_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]
+    size = os.path.getsize(path) if os.path.isfile(path) else 0
+    return _audio_probe(lambda *rest: L.afec_audio_probe_file(str(path).encode(), *rest), 2 * size + 16)
+
+
 def crawl(images, names=None, devices=(0,), workers=None, files_per_batch=512, database=None, digests=False):
     """The low-level crawl: every per-frame record and its statistics into the low-level database.  images: list of bytes (WAV file images), or None: names are the paths of files on disk.  -> dict of statistics.
     workers: host threads per device; None = the library's choice (TCrawlOptions::mWorkersPerDevice = 0: from the CPUs the

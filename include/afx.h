@@ -315,7 +315,14 @@ enum {
   AFX_RAW_I24 = 1, /* packed little-endian int24 (S24BitTo16BitFloat, SampleConverter.h:474-486)       */
   AFX_RAW_F32 = 2, /* float in [-1, 1]           (S0To1FloatTo16BitFloat, SampleConverter.h:529-533)   */
   AFX_RAW_I32 = 3, /* int32                      (S32BitSignedTo16BitFloat, SampleConverter.h:514-518) */
-  AFX_RAW_F64 = 4  /* double in [-1, 1]          (S0To1FloatTo16BitFloat, SampleConverter.h:529-533)   */
+  AFX_RAW_F64 = 4, /* double in [-1, 1]          (S0To1FloatTo16BitFloat, SampleConverter.h:529-533)   */
+  /* The same five with the bytes of each sample in Motorola (big-endian) order, as an AIFF's sample data holds them.
+   * They are made native on the GPU, in place in the library's own copy; the caller's memory is only read. */
+  AFX_RAW_I16_BE = 5,
+  AFX_RAW_I24_BE = 6,
+  AFX_RAW_F32_BE = 7,
+  AFX_RAW_I32_BE = 8,
+  AFX_RAW_F64_BE = 9
 };
 typedef struct {
   const void* data;    /* host pointer, interleaved by channel */
