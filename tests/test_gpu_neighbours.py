@@ -152,6 +152,27 @@ def test_autocorrelation_looks_past_the_last_frame_when_the_buffer_has_more(plan
     assert abs(cut[1, NEIGH_FIELDS["auto_correlation"]] - ref[1, NEIGH_FIELDS["auto_correlation"]]) > 1e-6
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_autocorrelation_of_a_pair_with_a_silent_partner(plan, oracle, dtype):
+    """acorr_kernel puts two frames through one complex transform: a frame whose segment is zeros must give exactly 0
+    (Autocorrelation.cpp:97-105), not the rounding noise its live partner leaves in its half.  Blocks of 4 096 samples,
+    zeros and noise in turn: as it is the buffer pairs zero frames with zero frames, without its first hop it pairs a zero
+    frame with a live one in either order"""
+    n = 2048 + 1024 * 20
+    x = np.random.default_rng(9).uniform(-1, 1, n).astype(dtype)
+    x[(np.arange(n) // 4096) % 2 == 0] = 0.0
+    bufs = [x, x[1024:]]
+    res = plan.extract(bufs, afx.D_AUTO_CORRELATION)
+    ref = np.concatenate([oracle.run_neighbours(b.astype(np.float64)) for b in bufs])[:, NEIGH_FIELDS["auto_correlation"]]
+    assert res["frame_offset"].tolist() == [0, 21, 41]
+    zero = ref == 0.0
+    mixed = zero[21::2] != zero[22::2]          # the shifted buffer's pairs (2 i, 2 i + 1)
+    assert mixed.any() and (zero[21::2] & mixed).any() and (zero[22::2] & mixed).any() and (zero[0:20:2] & zero[1:21:2]).any()
+    rtol, atol = _tol.NEIGH_TOL["auto_correlation"]
+    _tol.check_gpu("auto_correlation", res["auto_correlation"], ref, rtol, atol, what=f"{np.dtype(dtype).name} ")
+    np.testing.assert_array_equal(res["auto_correlation"][zero], 0.0)
+
+
 def test_statistics_of_the_neighbour_series(plan, oracle):
     rng = np.random.default_rng(15)
     bufs = [b.astype(np.float32) for b in seeded_buffers(rng)[:4]]

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Per-section instruction budget of a kernel's frame loop: a copy of the kernel's source gets a scheduling barrier and an
 assembly comment at every section boundary, is compiled to ISA (hipcc -S --cuda-device-only), and the instructions between
-the markers are counted by kind.  (The scheduler still moves some work across the markers.)  The band kernel's sections are
-its stages: a marker stands in front of the kernel's call of each.
+the markers are counted by kind.  (The scheduler still moves some work across the markers.)  The sections are the kernel's
+stages: a marker stands in front of the kernel's call of each, and for a stage that stayed in the kernel as a block (the pitch
+kernel's two transforms, its correlation spectrum, hand-over, squared differences and first-dip search) at the block's head.
 
 usage: tools/section_budget.py bands|pitch"""
 import collections
@@ -15,8 +16,9 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 def at_call(stage):
-    """marker in front of the kernel's first statement that calls the stage, named as the stage"""
-    return (re.compile(r"^.*\b%s\(.*$" % stage, re.M), stage, True)
+    """marker in front of the kernel's first statement that calls the stage (with or without template arguments), named as
+    the stage"""
+    return (re.compile(r"^.*\b%s(<[^>(]*>)?\(.*$" % stage, re.M), stage, True)
 
 
 KERNELS = {
@@ -29,17 +31,17 @@ KERNELS = {
                   "park_frame", "finish_group")] +
               [("        // this frame is the next one", "tail", True)]),
     "pitch": ("afx_time.hip", "void pitch_kernel(const TimeArgs a)", r"_ZN3afx12_GLOBAL__N_112pitch_kernelIfLb1EEEvNS_8TimeArgsE", [
-        ("      cx<double> zn[16];", "convert + prefetch", True),
+        at_call("next_half"),
         ("      fft(zn, c);", "forward transform", True),
-        ("      const double sign = (lane & 1) ? -1.0 : 1.0;", "pair-wise spectral product", True),
-        ("      // the second half's transform is the next frame's first-half transform", "hand-over + blocked loads", True),
+        ("      // correlation spectrum: g = conj(8 Zc)", "correlation spectrum", True),
+        ("      // the second half's transform is the next frame's first-half transform", "hand-over", True),
+        at_call("request_blocked"),
         ("      fft(g, c);", "inverse transform", True),
-        ("      // c[2m] = Re F[m] / 1024", "to the blocked layout", True),
-        ("      // ---- squared-difference terms (pitchyinfast.c:96-117) ----", "hop descriptors + squares", True),
-        ("      double s0 = 0.0, s1 = 0.0;", "squared differences", True),
-        ("      // ---- cumulative mean normalisation", "cumulative mean normalisation", True),
-        ("      // ---- first dip below the tolerance", "minimum search", True),
-        ("      // fvec_quadratic_peak_pos", "interpolation + confidence", True)]),
+        at_call("to_blocked"), at_call("blocked_samples"), at_call("hop_descriptors"), at_call("square_halves"),
+        ("      // squared differences (pitchyinfast.c:96-117)", "squared differences", True),
+        at_call("cumulative_mean_normalise"),
+        ("      // first dip below the tolerance", "first dip or last minimum", True),
+        at_call("quadratic_peak_and_confidence"), at_call("store_pitch")]),
 }
 
 
