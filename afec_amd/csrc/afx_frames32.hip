@@ -339,11 +339,19 @@ struct Wave32 {
 // ---- E: real parts, then imaginary parts through the same plane (a wave's DS operations execute in order, so the
 // second round of writes needs no wait for the first round of reads); `queue_behind` issues what is to queue up behind
 // them (the first two groups of twiddles) ----
-template <class F>
+// SINGLE_STORES (MFCC class): every store its own ds_write_b64 -- volatile in the LDS address space, as the reads are --
+// instead of the 32 ds_write2_b64 the compiler merges the plain stores into: a ds_write2_b64 costs the store path 13
+// cycles, two ds_write_b64 about 12, and the loop measured 0.7-1.1 % faster (profiles/r15/ab_steps.txt).  The other
+// classes keep the merged stores (and their recorded registers and scratch).
+template <bool SINGLE_STORES, class F>
 __device__ __forceinline__ void exchange32(cx<double> (&v)[32], double* pw, lds_vdouble2* pr, F queue_behind) {
   double re[32], im[32];
+  auto store = [pw](int k1, double x) {
+    if constexpr (SINGLE_STORES) ((lds_vdouble*)pw)[kRowSlots * k1] = x;
+    else pw[kRowSlots * k1] = x;
+  };
 #pragma unroll
-  for (int k1 = 0; k1 < 32; ++k1) pw[kRowSlots * k1] = v[k1].re;
+  for (int k1 = 0; k1 < 32; ++k1) store(k1, v[k1].re);
 #pragma unroll
   for (int m = 0; m < 16; ++m) {
     const f64x2_t two = pr[m];
@@ -351,7 +359,7 @@ __device__ __forceinline__ void exchange32(cx<double> (&v)[32], double* pw, lds_
     re[2 * m + 1] = two.y;
   }
 #pragma unroll
-  for (int k1 = 0; k1 < 32; ++k1) pw[kRowSlots * k1] = v[k1].im;
+  for (int k1 = 0; k1 < 32; ++k1) store(k1, v[k1].im);
 #pragma unroll
   for (int m = 0; m < 16; ++m) {
     const f64x2_t two = pr[m];
@@ -848,7 +856,7 @@ __global__ __launch_bounds__(kWaves32 * 64) void frames32_kernel(const FrameArgs
       // of twiddles queue up behind them ----
       // twiddles by first-stage butterfly: group g = butterflies j = 2 g, 2 g + 1 on rows j, j + 8, j + 16, j + 24
       double2 t[32];
-      exchange32(v, pw, pr, [&] { load_tw(t, tw, 0); load_tw(t, tw, 1); });
+      exchange32<FEAT == 0>(v, pw, pr, [&] { load_tw(t, tw, 0); load_tw(t, tw, 1); });
       // ---- the next frame's new hop: LDS-DMA into the plane once the exchange reads have returned (the DMA is a
       // vector-memory operation: nothing else orders it behind this wave's DS reads).  The last frame of a chunk
       // re-reads its own hop (no branch: the loop body stays one basic block).
