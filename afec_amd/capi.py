@@ -97,9 +97,11 @@ EXPORTS = [
     "afx_model_evaluate_features", "afx_batch_fetch_class_decision", "afx_decide",
     "afx_batch_high_level_text_capacity", "afx_batch_fetch_high_level_text", "afx_format_json_g9",
     "afx_batch_high_level_row_capacity", "afx_batch_fetch_high_level_row", "afx_format_class_json",
+    "afx_flac_probe", "afx_flac_build_index",
 ]
 RAW_I16, RAW_I24, RAW_F32, RAW_I32, RAW_F64 = 0, 1, 2, 3, 4
 RAW_I16_BE, RAW_I24_BE, RAW_F32_BE, RAW_I32_BE, RAW_F64_BE = 5, 6, 7, 8, 9   # the same with Motorola byte order (AIFF)
+RAW_FLAC = 10   # a FLAC stream, decoded on the GPU: afx_raw.data points at an afx_flac_stream (Plan.batch_from_raw takes the image)
 _RAW_BYTES = {RAW_I16: 2, RAW_I24: 3, RAW_F32: 4, RAW_I32: 4, RAW_F64: 8,
               RAW_I16_BE: 2, RAW_I24_BE: 3, RAW_F32_BE: 4, RAW_I32_BE: 4, RAW_F64_BE: 8}
 
@@ -163,6 +165,21 @@ class _Out(ctypes.Structure):
 class _Raw(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("format", ctypes.c_int32), ("channels", ctypes.c_int32),
                 ("sample_rate", ctypes.c_int32), ("reserved", ctypes.c_int32), ("n_frames", ctypes.c_int64)]
+
+
+class _FlacFrame(ctypes.Structure):   # afx_flac_frame
+    _fields_ = [("byte_off", ctypes.c_int64), ("first_sample", ctypes.c_int64)]
+
+
+class _FlacStream(ctypes.Structure):   # afx_flac_stream
+    _fields_ = [("frames", ctypes.c_void_p), ("frames_bytes", ctypes.c_int64), ("index", ctypes.c_void_p), ("n_index", ctypes.c_int32),
+                ("bits_per_sample", ctypes.c_int32), ("stream_channels", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class _FlacInfo(ctypes.Structure):   # afx_flac_info
+    _fields_ = [("sample_rate", ctypes.c_int32), ("channels", ctypes.c_int32), ("bits_per_sample", ctypes.c_int32),
+                ("min_blocksize", ctypes.c_int32), ("max_blocksize", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("total_samples", ctypes.c_int64), ("first_frame_off", ctypes.c_int64)]
 
 
 class _LoadInfo(ctypes.Structure):
@@ -294,6 +311,8 @@ def load_library():
     L.afx_batch_destroy.restype = None
     L.afx_batch_create_from_raw.argtypes = [vp, ctypes.POINTER(_Raw), i32, u32, ctypes.POINTER(vp), ctypes.POINTER(_LoadInfo)]
     L.afx_batch_fetch_samples.argtypes = [vp, i32, vp, i64]
+    L.afx_flac_probe.argtypes = [vp, i64, ctypes.POINTER(_FlacInfo)]
+    L.afx_flac_build_index.argtypes = [vp, i64, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i64)]
     L.afx_host_alloc.restype = vp
     L.afx_host_alloc.argtypes = [i64]
     L.afx_host_free.argtypes = [vp]
@@ -619,7 +638,8 @@ class Plan:
         return Batch(self, bufs, mask)
 
     def batch_from_raw(self, raws, mask=D_ALL_LOW_LEVEL):
-        """raws: list of (array, channels[, sample_rate]); array dtype int16 / int32 / float32 / float64 (interleaved,
+        """raws: list of (array, channels[, sample_rate]), or (FLAC image, None, None, RAW_FLAC);
+        array dtype int16 / int32 / float32 / float64 (interleaved,
         shape [frames*channels] or [frames, channels]) or uint8 of packed 24-bit little-endian samples; files at another
         sample_rate than the plan's are converted on the GPU (SampleAnalyser.cpp:563-607).
         Returns (Batch, list of load-info dicts): the LoadSample front end on the GPU."""
@@ -627,6 +647,18 @@ class Plan:
         arr = (_Raw * max(1, n))()
         keep = []
         for i, item in enumerate(raws):
+            if len(item) > 3 and item[3] is not None and int(item[3]) == RAW_FLAC:
+                # (FLAC image, channels or None, sample_rate or None, RAW_FLAC): indexed here on the host, decoded on the GPU;
+                # an image the indexer refuses goes on as a buffer the library refuses (status in buf_status)
+                # (or a ready _FlacStream, channels, sample_rate, RAW_FLAC, n_frames: the caller's own descriptor and memory)
+                if isinstance(item[0], _FlacStream):
+                    stream, holds, channels, rate, frames = item[0], item[0], int(item[1]), int(item[2]), int(item[4])
+                else:
+                    stream, holds, channels, rate, frames = flac_stream(item[0], self.L)
+                keep.append(holds)
+                arr[i].data = ctypes.addressof(stream) if stream is not None else None
+                arr[i].format, arr[i].channels, arr[i].sample_rate, arr[i].n_frames = RAW_FLAC, channels, rate, frames
+                continue
             data, channels = item[0], int(item[1])
             rate = int(item[2]) if len(item) > 2 else 0
             data = np.ascontiguousarray(np.asarray(data).reshape(-1))
@@ -659,6 +691,44 @@ class Plan:
         b.total_frames = int(self.L.afx_batch_total_frames(h))
         infos = [{k: getattr(info[i], k) for k, _ in _LoadInfo._fields_ if k != "reserved"} for i in range(n)]
         return b, infos
+
+
+def flac_probe(image, L=None):
+    """afx_flac_probe on a FLAC image (bytes or uint8 array) -> (status, dict of STREAMINFO's facts and first_frame_off)"""
+    L = L or load_library()
+    image = np.ascontiguousarray(np.frombuffer(image, dtype=np.uint8) if isinstance(image, (bytes, bytearray)) else image).view(np.uint8)
+    info = _FlacInfo()
+    st = L.afx_flac_probe(image.ctypes.data if image.size else None, image.size, ctypes.byref(info))
+    return st, {k: int(getattr(info, k)) for k, _ in _FlacInfo._fields_ if k != "reserved"}
+
+
+def flac_build_index(image, L=None):
+    """afx_flac_build_index -> (status, int64 [frames + 1, 2] of (byte offset from the first frame, first sample), total samples)"""
+    L = L or load_library()
+    image = np.ascontiguousarray(np.frombuffer(image, dtype=np.uint8) if isinstance(image, (bytes, bytearray)) else image).view(np.uint8)
+    n, total = ctypes.c_int32(), ctypes.c_int64()
+    src = image.ctypes.data if image.size else None
+    st = L.afx_flac_build_index(src, image.size, None, 0, ctypes.byref(n), ctypes.byref(total))
+    if st != -4:                                          # AFX_ERR_OUT_OF_MEMORY: the count, now with room
+        return st, np.zeros((0, 2), dtype=np.int64), 0
+    index = np.zeros((n.value + 1, 2), dtype=np.int64)
+    st = L.afx_flac_build_index(src, image.size, index.ctypes.data, n.value + 1, ctypes.byref(n), ctypes.byref(total))
+    return st, index, total.value
+
+
+def flac_stream(image, L=None, index=None):
+    """the afx_flac_stream of an image for afx_raw.data -> (_FlacStream or None, what must stay alive, afx_raw.channels,
+    sample_rate, n_frames).  `index`: the caller's own instead of the indexer's."""
+    st, info = flac_probe(image, L)
+    if st == 0 and index is None:
+        st, index, total = flac_build_index(image, L)
+    if st != 0:
+        return None, None, 1, 0, 0
+    image = np.ascontiguousarray(np.frombuffer(image, dtype=np.uint8) if isinstance(image, (bytes, bytearray)) else image).view(np.uint8)
+    index = np.ascontiguousarray(index, dtype=np.int64)
+    frames = image[info["first_frame_off"]:info["first_frame_off"] + int(index[-1, 0])]
+    s = _FlacStream(frames.ctypes.data, frames.size, index.ctypes.data, len(index) - 1, info["bits_per_sample"], info["channels"], 0)
+    return s, (s, image, frames, index), min(info["channels"], 2), info["sample_rate"], int(index[-1, 1])
 
 
 class Model:

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "afx_host.h"
+#include "flac/afx_flac.h"
 #include "rawpcm/afx_rawpcm.h"
 
 namespace afx {
@@ -17,6 +18,9 @@ namespace afx {
 // file from a fixed list without it, find it null and refuse big-endian buffers
 extern hipError_t launch_raw_native(unsigned char* raw, const RawNativeFile* files, int n_files, int64_t n_tiles, hipStream_t stream)
     __attribute__((weak));
+// likewise the FLAC decoder (flac/afx_flac.hip): absent from the mock builds, which refuse an AFX_RAW_FLAC buffer
+extern hipError_t launch_flac_decode(unsigned char* raw, const FlacFile* files, int n_files, int64_t n_frames, int64_t n_tiles,
+                                     int32_t* status, hipStream_t stream) __attribute__((weak));
 
 namespace host {
 
@@ -65,6 +69,20 @@ int native_twin(int format) {
     default: return -1;
   }
 }
+
+// A FLAC buffer as the caller describes it: the native format its samples are decoded to (-1: a depth that is not
+// decoded), and whether the descriptor and its index can be handed to the kernels as they are.  The kernels form every
+// address from the index, so it is held to: {0, 0} first, offsets and samples strictly rising, no frame above
+// kMaxFrameBytes or kMaxBlocksize, the sentinel equal to the stream's bytes and the buffer's sample count.
+int flac_native_format(const afx_flac_stream& s) {
+  return s.bits_per_sample == 16 || s.bits_per_sample == 8 ? AFX_RAW_I16 : s.bits_per_sample == 24 ? AFX_RAW_I24 : -1;
+}
+bool flac_descriptor_ok(const afx_raw& f, const afx_flac_stream& s) {
+  if (!s.frames || !s.index || s.n_index < 1 || s.frames_bytes < 1 || s.frames_bytes >= ((int64_t)1 << 40)) return false;
+  if (s.stream_channels < 1 || s.stream_channels > 8 || f.channels != std::min(s.stream_channels, 2)) return false;
+  return flac::index_ok(s.index, s.n_index, s.frames_bytes, f.n_frames);
+}
+inline int64_t pad16(int64_t bytes) { return (bytes + 15) & ~(int64_t)15; }
 
 struct CallerBuffers {   // fill() of afx_batch_create: the caller's PCM, one transfer per buffer
   const afx_buf* bufs;
@@ -138,6 +156,9 @@ struct RawBatch {
   std::vector<LoadPlace> place;         // [n_bufs]
   std::vector<int64_t> lengths;         // [n_bufs]: samples of the normalised, trimmed, padded buffer
   int64_t raw_bytes = 0, conv_bytes = 0, group_slots = 0, conv_blocks = 0, conv_max_in = 0;
+  std::vector<FlacFile> flac;           // AFX_RAW_FLAC files: decoded on the GPU first of all (their offsets: plan_flac)
+  std::vector<int32_t> flac_buf;        // their buffer indices
+  int64_t flac_bytes = 0, flac_frames = 0, flac_tiles = 0;   // their slots behind the PCM and the conversions' buffers
   Workspace* ws = nullptr;
   unsigned char* d_raw = nullptr;
   LoadFile* d_files = nullptr;
@@ -147,9 +168,32 @@ struct RawBatch {
 void lay_out_raw_arena(RawBatch& r) {
   for (int i = 0; i < r.n_bufs; ++i) {
     const afx_raw& f = r.raws[i];
+    r.files[(size_t)i] = LoadFile{0, 0, 0, 0};
+    if (f.format == AFX_RAW_FLAC) {
+      // the slot holds the decoded PCM of the first two channels; what goes up lies behind the batch's PCM (plan_flac)
+      const bool shaped = f.data && f.n_frames > 0 && f.n_frames < 0x7FFFFFFF && f.sample_rate >= 0;
+      if (!shaped) { r.status[(size_t)i] = AFX_ERR_BAD_BUFFER; continue; }
+      // a build without the decoder (the mock device) refuses the file like any other it cannot take, its descriptor unread
+      if (!launch_flac_decode) { r.status[(size_t)i] = AFX_ERR_UNSUPPORTED; continue; }
+      const afx_flac_stream& s = *(const afx_flac_stream*)f.data;
+      const int native = flac_native_format(s);
+      if (native < 0) { r.status[(size_t)i] = AFX_ERR_UNSUPPORTED; continue; }
+      if (!flac_descriptor_ok(f, s)) { r.status[(size_t)i] = AFX_ERR_BAD_BUFFER; continue; }
+      // the kernels' prefixes over frames and output tiles are 32-bit: the file that would take a batch beyond them is
+      // refused, for itself alone (as a conversion beyond the resampler's block count is)
+      if (r.flac_frames > 0x3FFFFFFF - s.n_index || r.flac_tiles > 0x7FFFFFFF - flac_output_tiles(f.n_frames)) {
+        r.status[(size_t)i] = AFX_ERR_UNSUPPORTED;
+        continue;
+      }
+      r.files[(size_t)i] = LoadFile{r.raw_bytes, f.n_frames, f.channels, native};
+      r.raw_bytes += pad16(f.n_frames * f.channels * raw_bytes_per_sample(native));
+      r.flac_buf.push_back(i);
+      r.flac_frames += s.n_index;
+      r.flac_tiles += flac_output_tiles(f.n_frames);
+      continue;
+    }
     const int bps = raw_bytes_per_sample(f.format);
     const bool good = bps && f.data && f.n_frames > 0 && f.n_frames < 0x7FFFFFFF && f.channels >= 1 && f.channels <= 8 && f.sample_rate >= 0;
-    r.files[(size_t)i] = LoadFile{0, 0, 0, 0};
     if (!good) { r.status[(size_t)i] = AFX_ERR_BAD_BUFFER; continue; }
     // a build without the byte-order kernel (the mock device) refuses a big-endian file like any other it cannot take
     if (native_twin(f.format) >= 0 && !launch_raw_native) { r.status[(size_t)i] = AFX_ERR_UNSUPPORTED; continue; }
@@ -185,7 +229,7 @@ void plan_conversions(RawBatch& r) {
       continue;
     }
     ResampleFile c{};
-    c.raw_off = r.files[(size_t)i].raw_off; c.n_in = f.n_frames; c.channels = f.channels; c.format = f.format; c.factor = factor;
+    c.raw_off = r.files[(size_t)i].raw_off; c.n_in = f.n_frames; c.channels = f.channels; c.format = r.files[(size_t)i].format; c.factor = factor;
     c.n_out = std::max<int64_t>(1, (int64_t)n_out_d);
     c.mono_off = r.raw_bytes + r.conv_bytes;
     r.conv_bytes += ((c.n_in + 2 * kResampleMargin) * 4 + 15) & ~(int64_t)15;
@@ -201,12 +245,86 @@ void plan_conversions(RawBatch& r) {
   }
 }
 
+// The slots of the FLAC files behind the batch's PCM and the conversions' buffers, the way plan_conversions places its
+// own: per file the frames as they lie in the file and behind them the index (the order a staging buffer holds them in,
+// so one transfer can move both), then the decoder's int32 work area, subframe records and channel assignments; behind
+// all files the kernels' table and the status words.  Every slot starts on a 16-byte boundary and is padded to one.
+void plan_flac(RawBatch& r) {
+  std::vector<int32_t> kept;
+  r.flac_frames = r.flac_tiles = 0;   // lay_out_raw_arena's sums bounded them; now over the files that are still good
+  const int64_t base = r.raw_bytes + r.conv_bytes;
+  for (int32_t i : r.flac_buf) {
+    if (r.status[(size_t)i] != AFX_OK) continue;   // refused by plan_conversions
+    const afx_flac_stream& s = *(const afx_flac_stream*)r.raws[i].data;
+    FlacFile f{};
+    f.out_off = r.files[(size_t)i].raw_off;
+    f.n_samples = r.raws[i].n_frames; f.n_index = s.n_index; f.bits = s.bits_per_sample; f.stream_channels = s.stream_channels;
+    f.bytes_off = base + r.flac_bytes;
+    r.flac_bytes += pad16(s.frames_bytes);
+    f.index_off = base + r.flac_bytes;
+    r.flac_bytes += ((int64_t)s.n_index + 1) * (int64_t)sizeof(afx_flac_frame);
+    f.frame_first = (int32_t)r.flac_frames;
+    f.tile_first = (int32_t)r.flac_tiles;
+    r.flac_frames += s.n_index;
+    r.flac_tiles += flac_output_tiles(f.n_samples);
+    r.flac.push_back(f);
+    kept.push_back(i);
+  }
+  // what is written on the device only, behind everything that goes up
+  for (FlacFile& f : r.flac) {
+    f.work_off = base + r.flac_bytes;
+    r.flac_bytes += pad16(f.n_samples * f.stream_channels * 4);
+    f.sub_off = base + r.flac_bytes;
+    r.flac_bytes += (int64_t)f.n_index * f.stream_channels * (int64_t)sizeof(flac::Subframe);
+    f.assign_off = base + r.flac_bytes;
+    r.flac_bytes += pad16((int64_t)f.n_index * 4);
+  }
+  r.flac_buf.swap(kept);
+}
+int64_t flac_table_bytes(const RawBatch& r) { return pad16((int64_t)(r.flac.size() * sizeof(FlacFile))); }
+
+// A batch with FLAC files: what goes up is a list of pieces (a native file's PCM; a FLAC's frames and its index).  Pieces
+// that follow each other in host memory as they do in the arena, with less than 16 bytes of padding between them, travel
+// as one run; a batch that is one run goes through the plan's upload stream like a staging buffer of PCM.
+hipError_t upload_pieces(RawBatch& r) {
+  struct Piece { const char* src; int64_t dst, bytes; };
+  std::vector<Piece> runs;
+  auto add = [&runs](const void* src, int64_t dst, int64_t bytes) {
+    if (!runs.empty()) {
+      Piece& last = runs.back();
+      const int64_t gap = dst - (last.dst + last.bytes);
+      if (gap >= 0 && gap < 16 && (const char*)src - last.src == dst - last.dst) { last.bytes = dst + bytes - last.dst; return; }
+    }
+    runs.push_back(Piece{(const char*)src, dst, bytes});
+  };
+  size_t next_flac = 0;
+  for (int i = 0; i < r.n_bufs; ++i) {
+    if (r.status[(size_t)i] != AFX_OK) continue;
+    const afx_raw& f = r.raws[i];
+    if (f.format != AFX_RAW_FLAC) {
+      add(f.data, r.files[(size_t)i].raw_off, f.n_frames * f.channels * raw_bytes_per_sample(f.format));
+    } else {
+      const afx_flac_stream& s = *(const afx_flac_stream*)f.data;
+      const FlacFile& d = r.flac[next_flac++];
+      add(s.frames, d.bytes_off, s.frames_bytes);
+      add(s.index, d.index_off, ((int64_t)s.n_index + 1) * (int64_t)sizeof(afx_flac_frame));
+    }
+  }
+  if (runs.size() == 1) return upload_through_plan(r.plan, r.ws, r.d_raw + runs[0].dst, runs[0].src, (size_t)runs[0].bytes);
+  for (const Piece& p : runs) {
+    const hipError_t e = hipMemcpyAsync(r.d_raw + p.dst, p.src, (size_t)p.bytes, hipMemcpyHostToDevice, r.ws->stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // the decoded PCM into the workspace's raw arena
 hipError_t upload_raw(RawBatch& r, const char** what) {
   // Files that lie back to back in host memory, each starting at the next 16-byte boundary (a pipeline's staging
   // buffer), have the layout of the device arena: one transfer moves them all.  Otherwise one transfer per file
   // (each costs ~10 us of runtime overhead, which dominates for thousands of short files).
   *what = "hipMemcpy(raw)";
+  if (!r.flac.empty()) return upload_pieces(r);
   bool contiguous = true;
   const char* base = nullptr;
   for (int i = 0; i < r.n_bufs && contiguous; ++i)
@@ -288,7 +406,12 @@ hipError_t stage_and_scan(RawBatch& r, const char** what) {
   const size_t tables_bytes = be.empty() ? files_bytes : be_off + be_bytes;
   const size_t scan_off = (tables_bytes + 63) & ~(size_t)63;
   *what = "hipMalloc(raw staging)";
-  if ((e = ws_reserve(plan, ws->raw, (size_t)(r.raw_bytes + r.conv_bytes) + 16)) != hipSuccess) return e;
+  // a batch with FLAC files: their slots, the decoder's table and one status word per file behind everything else in the arena
+  const int64_t flac_table_off = r.raw_bytes + r.conv_bytes + r.flac_bytes, flac_status_off = flac_table_off + flac_table_bytes(r);
+  const size_t flac_status_bytes = r.flac.size() * sizeof(int32_t);
+  const size_t flac_tail = r.flac.empty() ? 0 : (size_t)(r.flac_bytes + flac_table_bytes(r) + pad16((int64_t)flac_status_bytes));
+  const size_t status_pin_off = (scan_off + scan_bytes + 63) & ~(size_t)63, pin_bytes = r.flac.empty() ? scan_off + scan_bytes : status_pin_off + flac_status_bytes;
+  if ((e = ws_reserve(plan, ws->raw, (size_t)(r.raw_bytes + r.conv_bytes) + flac_tail + 16)) != hipSuccess) return e;
   if ((e = ws_reserve(plan, ws->files, tables_bytes)) != hipSuccess) return e;
   if ((e = ws_reserve(plan, ws->scan, r.scan.size() * sizeof(LoadScan))) != hipSuccess) return e;
   if ((e = ws_reserve(plan, ws->partial, (size_t)n_bufs * load_scan_blocks_per_file(n_bufs) * 16)) != hipSuccess) return e;
@@ -299,13 +422,28 @@ hipError_t stage_and_scan(RawBatch& r, const char** what) {
     // Both tables in ONE copy, enqueued before the PCM goes up: the file table is known on the host already (the
     // converted files' entries included), so nothing but the kernel's launch stands between the upload and the scan.
     *what = "raw_native";
-    if ((e = ws_pin_reserve(ws, scan_off + scan_bytes)) != hipSuccess) return e;
+    if ((e = ws_pin_reserve(ws, pin_bytes)) != hipSuccess) return e;
     std::memcpy(ws->h_pin, r.files.data(), files_bytes);
     plan_converted_files(r, (LoadFile*)ws->h_pin);
     std::memcpy((unsigned char*)ws->h_pin + be_off, be.data(), be_bytes);
     if ((e = hipMemcpyAsync(r.d_files, ws->h_pin, tables_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
   }
+  if (!r.flac.empty()) {
+    // the decoder's table, and its status words cleared (pageable source: the copy has left `flac` when the scan below
+    // has been waited for, as the conversions' table has)
+    *what = "flac_decode";
+    if ((e = ws_pin_reserve(ws, pin_bytes)) != hipSuccess) return e;   // the block the status words come down into: sized once
+    if ((e = hipMemcpyAsync(r.d_raw + flac_table_off, r.flac.data(), r.flac.size() * sizeof(FlacFile), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(r.d_raw + flac_status_off, 0, flac_status_bytes, s)) != hipSuccess) return e;
+  }
   if ((e = upload_raw(r, what)) != hipSuccess) return e;
+  // FLAC frames become native PCM at their files' raw_off, ahead of everything that reads PCM (flac/afx_flac.hip)
+  if (!r.flac.empty()) {
+    *what = "flac_decode";
+    if ((e = launch_flac_decode(r.d_raw, (const FlacFile*)(r.d_raw + flac_table_off), (int)r.flac.size(), r.flac_frames, r.flac_tiles,
+                                (int32_t*)(r.d_raw + flac_status_off), s)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync((unsigned char*)ws->h_pin + status_pin_off, r.d_raw + flac_status_off, flac_status_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  }
   // behind the upload as load_scan is: upload_through_plan returns when its transfer has landed (the host waits,
   // afx_workspace.cpp), the per-file copies are on `s` themselves
   if (!be.empty()) {
@@ -327,7 +465,7 @@ hipError_t stage_and_scan(RawBatch& r, const char** what) {
   // the file table up and the scan results down through the workspace's page-locked block (pageable copies are staged
   // by the runtime on this thread and complete through its event thread: host CPU a crawl's workers do not have to spend)
   if (be.empty()) {
-    if ((e = ws_pin_reserve(ws, scan_off + scan_bytes)) != hipSuccess) return e;
+    if ((e = ws_pin_reserve(ws, pin_bytes)) != hipSuccess) return e;
     std::memcpy(ws->h_pin, r.files.data(), files_bytes);
     if ((e = hipMemcpyAsync(r.d_files, ws->h_pin, files_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
   }
@@ -338,6 +476,12 @@ hipError_t stage_and_scan(RawBatch& r, const char** what) {
   *what = "hipStreamSynchronize";
   if ((e = wait_for_stream(ws, s)) != hipSuccess) return e;
   std::memcpy(r.scan.data(), (const unsigned char*)ws->h_pin + scan_off, scan_bytes);
+  // a frame whose CRC-16 or structure did not hold fails its file; what the scan read of it is dropped with it
+  for (size_t k = 0; k < r.flac.size(); ++k)
+    if (((const int32_t*)((const unsigned char*)ws->h_pin + status_pin_off))[k] != 0) {
+      r.status[(size_t)r.flac_buf[k]] = AFX_ERR_BAD_BUFFER;
+      r.files[(size_t)r.flac_buf[k]] = LoadFile{0, 0, 0, 0};
+    }
   return hipSuccess;
 }
 
@@ -419,6 +563,7 @@ int afx_batch_create_from_raw(afx_plan* plan, const afx_raw* raws, int32_t n_buf
   r.lengths.assign((size_t)n_bufs, 0);
   lay_out_raw_arena(r);
   plan_conversions(r);
+  if (!r.flac_buf.empty()) plan_flac(r);
 
   const long long t_begin = now_ns();
   // device staging of the decoded PCM and the scan results lives in the batch's pooled workspace

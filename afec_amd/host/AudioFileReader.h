@@ -1,7 +1,7 @@
 // afec_amd/host/AudioFileReader.h -- what the crawler needs of a container reader that is not TWaveFile, as an interface
 // that lives in this header alone.  afec_amd/host/Crawler.cpp is also linked into the mock-device builds of tests/sanitize
-// from a fixed list of files that cannot include AifFile.cpp: it reaches TAifFile through this interface and the weak factory
-// below, and so names no symbol of AifFile.cpp -- not even its type information, which the sanitizer builds' checks of
+// from a fixed list of files that cannot include AifFile.cpp or FlacFile.cpp: it reaches TAifFile and TFlacFile through this
+// interface and the weak factories below, and so names no symbol of AifFile.cpp or FlacFile.cpp -- not even its type information, which the sanitizer builds' checks of
 // virtual calls would otherwise ask for.
 #pragma once
 
@@ -32,5 +32,7 @@ public:
 
 // a new TAifFile (AifFile.cpp); the caller deletes it.  Crawler.cpp refers to it weakly and checks for null.
 TAudioFileReader* NewAifFile();
+// likewise a new TFlacFile (FlacFile.cpp, which needs the C-ABI's FLAC indexer: no part of the mock builds either)
+TAudioFileReader* NewFlacFile();
 
 }  // namespace afec

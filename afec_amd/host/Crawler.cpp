@@ -21,17 +21,20 @@
 #include "SqlitePool.h"
 #include "WaveFile.h"
 #include "AudioFileReader.h"
+#include "../csrc/flac/afx_flac_decode.h"   // sizeof(afx::flac::Subframe): what DeviceBytesOf counts per subframe
 
 namespace afec {
 
 // A weak reference: libafx_host.so holds AifFile.cpp; the mock-device builds of tests/sanitize link this file from a fixed
 // list without it, find the factory null and fail an AIFF like any other file they cannot read (AudioFileReader.h)
 TAudioFileReader* NewAifFile() __attribute__((weak));
+TAudioFileReader* NewFlacFile() __attribute__((weak));
 
-// TAifFile::SSupportedExtensions through gFileMatchesExtension (Directory.cpp:581-615): the end of the name, compared
+namespace {
+// a reader's SSupportedExtensions through gFileMatchesExtension (Directory.cpp:581-615): the end of the name, compared
 // without regard to case
-const char* AifFileTypeOf(const std::string& FileName) {
-  for (const char* pType : {"aiff", "aifc", "aif", "snd"}) {
+const char* ExtensionOf(const std::string& FileName, std::initializer_list<const char*> Types) {
+  for (const char* pType : Types) {
     const size_t n = std::strlen(pType) + 1;   // with the dot
     if (FileName.size() < n || FileName[FileName.size() - n] != '.') continue;
     bool Same = true;
@@ -39,6 +42,18 @@ const char* AifFileTypeOf(const std::string& FileName) {
     if (Same) return pType;
   }
   return nullptr;
+}
+}  // namespace
+
+const char* AifFileTypeOf(const std::string& FileName) { return ExtensionOf(FileName, {"aiff", "aifc", "aif", "snd"}); }
+const char* FlacFileTypeOf(const std::string& FileName) { return ExtensionOf(FileName, {"flac", "fla"}); }
+
+const char* FileTypeOf(const std::string& FileName, TReaderKind* pReader) {
+  const char* pType = AifFileTypeOf(FileName);
+  *pReader = TReaderKind::kAif;
+  if (!pType && (pType = FlacFileTypeOf(FileName))) *pReader = TReaderKind::kFlac;
+  if (!pType) { pType = "wav"; *pReader = TReaderKind::kWave; }   // every other name is a WAV's, as before
+  return pType;
 }
 
 namespace {
@@ -142,6 +157,14 @@ int64_t FileBytes(const TCrawlFile& f) {
   return ::stat(f.mFileName.c_str(), &St) == 0 ? (int64_t)St.st_size : 0;   // a file that is not there fails when it is opened
 }
 
+// what a file is expected to put into the staging buffer, before it is opened: its bytes, and for a FLAC (whose frames
+// are all of the file but the metadata) the index behind them, 16 bytes a frame -- a sixteenth of the file covers frames
+// of 256 bytes and more, which is every blocksize from 192 samples up in practice; StageBatch grows the buffer for the rest
+int64_t StagedBytesOf(const TCrawlFile& f) {
+  const int64_t Size = FileBytes(f);
+  return FlacFileTypeOf(f.mFileName) ? Size + Size / 16 + 32 : Size;
+}
+
 int64_t BytesPerSample(int Format) {
   switch (Format) {
     case AFX_RAW_I16: case AFX_RAW_I16_BE: return 2;
@@ -149,6 +172,12 @@ int64_t BytesPerSample(int Format) {
     case AFX_RAW_F64: case AFX_RAW_F64_BE: return 8;
     default: return 4;
   }
+}
+
+// what goes to the device for a file: its PCM, or a FLAC's frames (padded to 16 bytes) and index
+int64_t UploadBytesOf(const TDecodedSample& s) {
+  if (s.mFormat == AFX_RAW_FLAC) return ((s.mFlacFramesBytes + 15) & ~(int64_t)15) + ((int64_t)s.mFlacFrames + 1) * (int64_t)sizeof(afx_flac_frame);
+  return s.mNumberOfSampleFrames * s.mNumberOfChannels * BytesPerSample(s.mFormat);
 }
 
 // a digest of everything the device returned for file k of a batch (TCrawlOptions::mRowDigests); never 0, which says
@@ -177,7 +206,7 @@ struct TWork {
   std::unique_ptr<TFinishedBatch> mpDone;
   std::vector<TDecodedSample> mDecoded;
   int mOrdinal = 0;          // batches in the order they were cut; the halves of a batch keep the whole's
-  int64_t mFileBytes = 0;    // the files' sizes: what the staging buffer is sized from
+  int64_t mFileBytes = 0;    // what the files are expected to stage (StagedBytesOf): what the staging buffer is sized from
 };
 
 // One crawl: what its W workers per device and its one writer share, and the steps they take.  Lives for one call of
@@ -280,7 +309,7 @@ private:
       Begin = End = mCursor[(size_t)d];
       if (Begin >= Mine.size()) return false;
       while (End < Mine.size() && End - Begin < (size_t)mFilesPerBatch) {
-        const int64_t Size = FileBytes(*Mine[End]);
+        const int64_t Size = StagedBytesOf(*Mine[End]);
         if (End > Begin && Work.mFileBytes + Size > mBytesPerBatch) break;
         Work.mFileBytes += Size;
         ++End;
@@ -302,7 +331,8 @@ private:
   // Parse: every file's samples go straight to their place in the page-locked staging buffer (the device arena's layout:
   // payloads back to back, 16-byte aligned, so that the C-ABI uploads the batch in one transfer): a memcpy out of
   // a file image, a pread out of the page cache for a file on disk.  The buffer is sized from the files' sizes
-  // up front; only 8-bit files (widened to int16) can make it grow on the way.
+  // up front (StagedBytesOf); 8-bit files (widened to int16) and a FLAC of frames shorter than 256 bytes (its index is
+  // then more than the sixteenth allowed for) can make it grow on the way, with its contents kept.
   void StageBatch(TWork& Work, TPinned& Staging) {
     const double tParse0 = Now(), cParse0 = ThreadCpuSeconds();
     TFinishedBatch& Done = *Work.mpDone;
@@ -312,7 +342,7 @@ private:
     size_t Bytes = 0;
     Staging.Reserve((size_t)Work.mFileBytes + 16 * n + 64);
     TWaveFile Wave;
-    std::unique_ptr<TAudioFileReader> pAif;   // made by the first AIFF of the batch
+    std::unique_ptr<TAudioFileReader> pAif, pFlac;   // made by the first AIFF / FLAC of the batch
     // the same steps for either reader
     auto Stage = [&](auto& File, const char* pFileType, size_t i) {
       try {
@@ -342,12 +372,19 @@ private:
       }
     };
     for (size_t i = 0; i < n; ++i) {
-      // by extension, as TAudioFile::SCreateFromFile does (AudioFile.cpp:186-234); every other name is a WAV's, as before
-      const char* pAifType = AifFileTypeOf(Done.mFiles[i]->mFileName);
-      if (!pAifType) { Stage(Wave, "wav", i); continue; }
-      if (!pAif && NewAifFile) pAif.reset(NewAifFile());
-      if (pAif) Stage(*pAif, pAifType, i);
-      else Done.mFailed[i] = "Sample failed to load: AIFF files are not supported by this build.";
+      // by extension, as TAudioFile::SCreateFromFile does (AudioFile.cpp:186-244); every other name is a WAV's, as before
+      TReaderKind Reader;
+      const char* pType = FileTypeOf(Done.mFiles[i]->mFileName, &Reader);
+      if (Reader == TReaderKind::kWave) { Stage(Wave, pType, i); continue; }
+      if (Reader == TReaderKind::kAif) {
+        if (!pAif && NewAifFile) pAif.reset(NewAifFile());
+        if (pAif) Stage(*pAif, pType, i);
+        else Done.mFailed[i] = "Sample failed to load: AIFF files are not supported by this build.";
+        continue;
+      }
+      if (!pFlac && NewFlacFile) pFlac.reset(NewFlacFile());
+      if (pFlac) Stage(*pFlac, pType, i);
+      else Done.mFailed[i] = "Sample failed to load: FLAC files are not supported by this build.";
     }
     for (size_t k = 0; k < Decoded.size(); ++k) Decoded[k].mpInterleavedSamples = (char*)Staging.mp + Offset[k];
     std::lock_guard<std::mutex> Lock(mStatMutex);
@@ -360,7 +397,13 @@ private:
   // than its bytes on disk: a header that claims a low sampling rate)
   int64_t DeviceBytesOf(const TDecodedSample& s) const {
     const int64_t Converted = TSampleAnalyser::ConvertedSampleFrames(s, mOptions.mSampleRate);
-    return Converted * 16 + s.mNumberOfSampleFrames * s.mNumberOfChannels * 4;
+    int64_t Bytes = Converted * 16 + s.mNumberOfSampleFrames * s.mNumberOfChannels * 4;
+    // a FLAC besides: its frames and index as they go up, the decoder's int32 work area over ALL of the stream's channels,
+    // one record per subframe and one word per frame (afec_amd/csrc/afx_batch_create.cpp, plan_flac)
+    if (s.mFormat == AFX_RAW_FLAC)
+      Bytes += UploadBytesOf(s) + s.mNumberOfSampleFrames * s.mFlacStreamChannels * 4 +
+               (int64_t)s.mFlacFrames * (s.mFlacStreamChannels * (int64_t)sizeof(afx::flac::Subframe) + 4) + 128;
+    return Bytes;
   }
 
   // ---- one batch on the GPU, with the reference's failure semantics (SampleAnalyser.cpp:368-408: a file that cannot
@@ -501,7 +544,7 @@ private:
     const TRecordBatch& R = Work.mpDone->mResults;
     const int64_t n = (int64_t)Work.mpDone->mFiles.size(), Analysed = (int64_t)Work.mDecoded.size();
     int64_t Frames = 0, ResultBytes = 0, PcmBytes = 0;
-    for (const TDecodedSample& s : Work.mDecoded) PcmBytes += s.mNumberOfSampleFrames * s.mNumberOfChannels * BytesPerSample(s.mFormat);
+    for (const TDecodedSample& s : Work.mDecoded) PcmBytes += UploadBytesOf(s);
     if (Analysed && mpMode) {
       Frames = Work.mpDone->mModeFrames;
       ResultBytes = Work.mpDone->mModeResultBytes;
@@ -816,17 +859,20 @@ int AudioProbeByName(const char* name, const void* image, int64_t size, int64_t*
                      char* file_type, int32_t file_type_size, char* error, int32_t error_size) {
   try {
     const std::string Name = name ? name : "";
-    const char* pAifType = afec::AifFileTypeOf(Name);
-    if (file_type && file_type_size > 0) std::snprintf(file_type, (size_t)file_type_size, "%s", pAifType ? pAifType : "wav");
-    if (!pAifType) {
+    afec::TReaderKind Reader;
+    const char* pType = afec::FileTypeOf(Name, &Reader);
+    if (file_type && file_type_size > 0) std::snprintf(file_type, (size_t)file_type_size, "%s", pType);
+    if (Reader == afec::TReaderKind::kWave) {
       afec::TWaveFile Wave;
       if (image) Wave.OpenForRead(image, (size_t)size, Name); else Wave.OpenForRead(Name);
       return AudioProbe(Wave, props, payload, payload_capacity);
     }
-    if (!afec::NewAifFile) throw afec::TReadableException("AIFF files are not supported by this build.");
-    std::unique_ptr<afec::TAudioFileReader> pAif(afec::NewAifFile());
-    if (image) pAif->OpenForRead(image, (size_t)size, Name); else pAif->OpenForRead(Name);
-    return AudioProbe(*pAif, props, payload, payload_capacity);
+    const bool Flac = Reader == afec::TReaderKind::kFlac;
+    if (!(Flac ? afec::NewFlacFile : afec::NewAifFile))
+      throw afec::TReadableException(Flac ? "FLAC files are not supported by this build." : "AIFF files are not supported by this build.");
+    std::unique_ptr<afec::TAudioFileReader> pFile(Flac ? afec::NewFlacFile() : afec::NewAifFile());
+    if (image) pFile->OpenForRead(image, (size_t)size, Name); else pFile->OpenForRead(Name);
+    return AudioProbe(*pFile, props, payload, payload_capacity);
   } catch (const std::exception& e) {
     if (error && error_size > 0) std::snprintf(error, (size_t)error_size, "%s", e.what());
     return -1;

@@ -219,6 +219,11 @@ TCrawlStatistics CrawlOnKeptCrawler(const std::vector<TCrawlFile>& Files, const 
 // "aif" / "aiff" / "aifc" / "snd" when the name ends in that extension, in any case: the file goes to TAifFile and this is
 // its file_type_S; nullptr for every other name, which goes to TWaveFile (the reference's dispatch, AudioFile.cpp:186-234)
 const char* AifFileTypeOf(const std::string& FileName);
+// "flac" / "fla" likewise: the file goes to TFlacFile (TFlacFile::SSupportedExtensions, FlacFile.cpp:1084-1091)
+const char* FlacFileTypeOf(const std::string& FileName);
+// the dispatch by extension (AudioFile.cpp:237-244): file_type_S and, through *pReader, who reads the file
+enum class TReaderKind { kWave, kAif, kFlac };
+const char* FileTypeOf(const std::string& FileName, TReaderKind* pReader);
 // the statistics in the layout afec_crawl_wave_images_ex documents; any pointer may be NULL
 void StoreCrawlStatistics(const TCrawlStatistics& s, int32_t n_files, int32_t n_devices, double* stats, double* device_stats,
                           uint64_t* row_digests, double* crawl_facts);

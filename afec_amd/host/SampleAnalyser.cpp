@@ -115,9 +115,16 @@ std::vector<TSampleDataInfo> InfoOf(const std::vector<afx_load_info>& Info) {
 void CreateFromFiles(afx_plan* pPlan, const std::vector<TDecodedSample>& Files, TBatchGuard& Batch, std::vector<afx_load_info>& Info,
                      uint32_t Mask = kEverything) {
   std::vector<afx_raw> Raws(Files.size());
-  for (size_t i = 0; i < Files.size(); ++i)
-    Raws[i] = {Files[i].mpInterleavedSamples, Files[i].mFormat, Files[i].mNumberOfChannels, Files[i].mSampleRate, 0,
-               Files[i].mNumberOfSampleFrames};
+  std::vector<afx_flac_stream> Streams(Files.size());   // of the FLAC files: their descriptors point into the caller's buffer
+  for (size_t i = 0; i < Files.size(); ++i) {
+    const TDecodedSample& f = Files[i];
+    Raws[i] = {f.mpInterleavedSamples, f.mFormat, f.mNumberOfChannels, f.mSampleRate, 0, f.mNumberOfSampleFrames};
+    if (f.mFormat != AFX_RAW_FLAC || !f.mpInterleavedSamples) continue;
+    const char* pFrames = (const char*)f.mpInterleavedSamples;
+    Streams[i] = {pFrames, f.mFlacFramesBytes, (const afx_flac_frame*)(pFrames + ((f.mFlacFramesBytes + 15) & ~(int64_t)15)), f.mFlacFrames,
+                  f.mFlacBitsPerSample, f.mFlacStreamChannels, 0};
+    Raws[i].data = &Streams[i];
+  }
   Info.resize(Files.size());
   const int Status = afx_batch_create_from_raw(pPlan, Raws.data(), (int32_t)Files.size(), Mask, &Batch.mpBatch, Info.data());
   if (Status != AFX_OK) Throw("GPU feature extraction failed", Status);

@@ -80,6 +80,13 @@ struct TDecodedSample {
   // SampleAnalyser.cpp:464-467; the final tempo's duration heuristics use them); 0 = as given above
   int mOriginalSampleRate = 0;
   int64_t mOriginalNumberOfSamples = 0;
+  // mFormat == AFX_RAW_FLAC: mpInterleavedSamples points at the stream's frames (first sync code .. end of the last frame),
+  // padded to 16 bytes and followed by afx_flac_frame[mFlacFrames + 1] (TFlacFile::ReadSampleData); mNumberOfChannels is
+  // min(mFlacStreamChannels, 2) and mNumberOfSampleFrames the stream's total -- what afx_flac_stream needs
+  int64_t mFlacFramesBytes = 0;
+  int mFlacFrames = 0;
+  int mFlacBitsPerSample = 0;
+  int mFlacStreamChannels = 0;
 };
 // what LoadSample leaves in TSampleData besides the samples (Export/SampleAnalyser.h:75-100)
 struct TSampleDataInfo {

@@ -322,8 +322,41 @@ enum {
   AFX_RAW_I24_BE = 6,
   AFX_RAW_F32_BE = 7,
   AFX_RAW_I32_BE = 8,
-  AFX_RAW_F64_BE = 9
+  AFX_RAW_F64_BE = 9,
+  /* A FLAC stream: afx_raw.data points at an afx_flac_stream (below), n_frames is the stream's sample count and channels
+   * is min(stream_channels, 2) -- the reference keeps the first two channels (FlacFile.cpp:576, 659).  The frames are
+   * decoded on the GPU into the native format of the stream's depth (16 -> I16, 24 -> I24, 8 -> I16 `v << 8`); a frame
+   * whose CRC-16 or structure does not hold fails its file (AFX_ERR_BAD_BUFFER in buf_status), never the batch. */
+  AFX_RAW_FLAC = 10
 };
+typedef struct { int64_t byte_off; int64_t first_sample; } afx_flac_frame;
+typedef struct {
+  const void* frames;            /* first frame's sync code .. end of the last frame */
+  int64_t frames_bytes;
+  const afx_flac_frame* index;   /* n_index + 1 entries; index[n_index] = {frames_bytes, total samples} */
+  int32_t n_index;
+  int32_t bits_per_sample;       /* STREAMINFO: 8, 16 or 24 */
+  int32_t stream_channels;       /* STREAMINFO: 1..8 */
+  int32_t reserved;
+} afx_flac_stream;
+/* The host's half of FLAC input (flac/afx_flac_index.cpp): touches no device, computes no CRC-16, decodes no residual. */
+typedef struct {
+  int32_t sample_rate, channels, bits_per_sample;
+  int32_t min_blocksize, max_blocksize, reserved;
+  int64_t total_samples;        /* STREAMINFO's; 0 = unknown, afx_flac_build_index finds it */
+  int64_t first_frame_off;      /* byte offset of the first frame in the image */
+} afx_flac_info;
+/* Skips a leading ID3v2 tag, requires `fLaC`, reads STREAMINFO and skips every other metadata block.
+ * AFX_ERR_BAD_BUFFER: no FLAC stream (no `fLaC`, truncated or missing STREAMINFO, no room for a frame behind the
+ * metadata).  AFX_ERR_UNSUPPORTED: Ogg-encapsulated FLAC, bits other than 8 / 16 / 24.  AFX_ERR_INVALID_ARG: null. */
+int afx_flac_probe(const void* image, int64_t bytes, afx_flac_info* info);
+/* Walks the frames of a probed image: index[k] = {byte offset from the first frame, first sample} and the end sentinel
+ * index[*n_index] = {frames' bytes, total samples}; needs capacity >= frames + 1 (AFX_ERR_OUT_OF_MEMORY otherwise, with
+ * *n_index = what is needed less one).  A frame start is accepted on its sync code, reserved bits, blocking strategy,
+ * header codes, CRC-8, agreement with STREAMINFO and the expected frame / sample number only.  AFX_ERR_BAD_BUFFER: a gap in
+ * the numbers, or the blocksizes' sum is not STREAMINFO's total. */
+int afx_flac_build_index(const void* image, int64_t bytes, afx_flac_frame* index, int32_t capacity, int32_t* n_index,
+                         int64_t* total_samples);
 typedef struct {
   const void* data;    /* host pointer, interleaved by channel */
   int32_t format;      /* AFX_RAW_* */
