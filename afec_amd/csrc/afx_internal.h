@@ -335,9 +335,8 @@ struct LoadPlace {   // per file, where the normalised samples go
   int64_t start_pad; // zeros in front (StartFrameOffset)
   double scaling;    // FinalScaling
 };
-// LoadFile::format of a converted file: mono floats already in the "16-bit float" range.  Internal to the device tables; its
-// value is also the public AFX_RAW_I16_BE's, which never reaches a device table (afx_batch_create.cpp: name_native_twins()
-// runs before this value is written, and a static_assert there names the coincidence)
+// LoadFile::format of a converted file: mono floats already in the "16-bit float" range.  Internal to the device tables,
+// which hold native formats only; its value coincides with the public AFX_RAW_I16_BE's, a format of afx_raw alone.
 constexpr int kRawMonoFloat = 5;
 int load_scan_blocks_per_file(int n_files);      // partial_scratch holds n_files x this x 16 bytes
 hipError_t launch_load_scan(const unsigned char* raw, const LoadFile* files, int n_files, double silence_floor,

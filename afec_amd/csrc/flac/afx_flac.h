@@ -1,7 +1,7 @@
 // afec_amd/csrc/flac/afx_flac.h -- the FLAC decode kernels (afx_flac.hip) and their launcher, shared with
 // afx_batch_create.cpp.  Kept apart from afx_internal.h for the reason highlevel/afx_highlevel.h gives.  The device mock
-// does NOT implement this launcher: afx_batch_create.cpp refers to it weakly and refuses an AFX_RAW_FLAC buffer where it
-// is absent.
+// does NOT implement this launcher: afx_batch_create.cpp refers to it weakly, and the plan of the raw arena
+// (afx_raw_plan.h) refuses an AFX_RAW_FLAC buffer where it is absent.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,7 +16,7 @@ constexpr int kFlacRestoreThreads = 64;   // one lane per kept subframe
 constexpr int kFlacOutputThreads = 256;   // one lane per sample frame; a workgroup takes a tile of 256 of one file
 
 // One FLAC file of a batch: where its pieces lie in the raw arena (byte offsets, each a multiple of 16).  The index is
-// the caller's, checked on the host before it goes up (afx_batch_create.cpp: offsets and samples strictly rising, frames
+// the caller's, checked on the host before it goes up (afx_raw_plan.h, flac_descriptor_ok: offsets and samples strictly rising, frames
 // of at most kMaxFrameBytes and kMaxBlocksize, the sentinel equal to frames_bytes / n_samples), so every address the
 // kernels form from it lies inside the file's own slots.
 struct FlacFile {

@@ -1,7 +1,7 @@
 // afec_amd/csrc/rawpcm/afx_rawpcm.h -- the byte-order kernel (afx_rawpcm.hip) and its launcher, shared with
 // afx_batch_create.cpp.  Kept apart from afx_internal.h for the reason highlevel/afx_highlevel.h gives.  The device mock
-// does NOT implement this launcher: afx_batch_create.cpp refers to it weakly and refuses a big-endian buffer where it is
-// absent.
+// does NOT implement this launcher: afx_batch_create.cpp refers to it weakly, and the plan of the raw arena
+// (afx_raw_plan.h) refuses a big-endian buffer where it is absent.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,7 +15,7 @@ constexpr int kRawNativeThreads = 256;
 constexpr int kRawNativeTileBytes = kRawNativeThreads * 48;   // 12 288
 
 // One big-endian file of a batch.  Its slot in the raw arena starts on a 16-byte boundary and is padded to one
-// (lay_out_raw_arena), so whole 16-byte vectors are read and written up to (bytes + 15) & ~15 and never beyond.
+// (afx_raw_plan.h: plan_raw_arena), so whole 16-byte vectors are read and written up to (bytes + 15) & ~15 and never beyond.
 struct RawNativeFile {
   int64_t raw_off;      // byte offset of the payload in the raw arena, a multiple of 16
   int64_t bytes;        // payload bytes (frames x channels x bytes per sample)
