@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import afec_amd as afx
-from tests import _tol
+from tests import _bands_ref, _tol
+from tests._bands_ref import contrast as contrast_from_magnitudes
 from tests._oracle import FIELDS, Oracle
 
 pytestmark = pytest.mark.gpu
@@ -22,25 +23,6 @@ def plan():
     p = afx.Plan(max_analysis_ms=0)
     yield p
     p.close()
-
-
-def contrast_from_magnitudes(mag):
-    """The reference's arithmetic (SA:2200-2232) on a given magnitude spectrum, in numpy: isolates the selection
-    and the sums from the FFT's rounding."""
-    counts = [2, 4, 6, 10, 12, 15, 17, 23, 29, 41, 61, 96, 148, 287]
-    out = np.zeros((mag.shape[0], 14))
-    for f in range(mag.shape[0]):
-        k = 1
-        for b, n in enumerate(counts):
-            band = np.sort(mag[f, k:k + n])
-            nn = max(1, int(0.3 * n))
-            valley = float(np.sum(band[:nn])) / nn + 1e-30
-            peak = float(np.sum(band[::-1][:nn])) / nn + 1e-30
-            mean = float(np.sum(mag[f, k:k + n])) / n if n >= 2 else float(mag[f, k])
-            with np.errstate(all="ignore"):
-                out[f, b] = -1.0 * np.power(peak / valley, 1.0 / np.log(mean + 1e-30))
-            k += n
-    return out
 
 
 def check_against_own_magnitudes(plan, x, what, rtol=1e-11):
@@ -90,6 +72,12 @@ def test_band_mean_next_to_one(plan):
 
 
 def test_ties_in_the_sort_keys(plan):
+    """What these inputs cover (counted on the CPU oracle with tests/_bands_ref.tie_census): `silence` has every bin equal,
+    so every cut goes through a class that is the whole band and takes exact_cut_sum's all-equal shortcut; `impulse` has
+    such whole-band classes too, with members that differ by <= 6.3e-16 relative, so the ordered walk runs but which member
+    it takes is invisible at 1e-11; `steps` and `tone` have no tie on any cut.  What they cannot cover: a wrong pick inside
+    a class, bins strictly beyond a class, and a class across the two sorted runs of bands 11 and 13 -- that is
+    tests/test_gpu_band_selection.py and the test below."""
     rng = np.random.default_rng(8)
     silence = np.zeros(2048 + 1024 * 2, np.float32)                       # every bin exactly 0: all keys equal
     impulse = np.zeros(2048 + 1024 * 2, np.float32); impulse[1500] = 0.8  # flat spectrum up to rounding: keys tie, doubles differ
@@ -100,11 +88,14 @@ def test_ties_in_the_sort_keys(plan):
 
 
 def test_quantised_spectrum_forces_the_slow_path(plan):
-    """Magnitudes that agree to 19 mantissa bits but differ below: built in the time domain from a sum of
-    bin-centred tones of nearly equal amplitude across one wide band."""
-    n = np.arange(2048 + 1024)
-    x = np.zeros(n.size)
-    rng = np.random.default_rng(17)
-    for k in range(470, 750):          # the 287-bin band (bins 465..751)
-        x += 1e-3 * (1.0 + 1e-9 * rng.uniform(-1, 1)) * np.sin(2 * np.pi * k * n / 2048.0 + rng.uniform(0, 6.28))
-    check_against_own_magnitudes(plan, x, "near-equal tones", rtol=1e-9)
+    """Magnitudes that agree to 19 mantissa bits but differ below: a tie-design buffer (tests/_bands_ref.py, design X),
+    whose 287-bin band has 40 such bins around the valley's cut with 60 bins below them, and 60 around the peak's with 50
+    above."""
+    oracle = Oracle()
+    x, _ = _bands_ref.tie_design("X", 3, np.float64, lambda period: oracle.run(period)[0, :1024])
+    res = check_against_own_magnitudes(plan, x, "tie design X", rtol=1e-11)
+    census = _bands_ref.tie_census(res["magnitude"])
+    for f in (0, 2):
+        for cut in (_bands_ref.VALLEY, _bands_ref.PEAK):
+            tie = census[f][13][cut]
+            assert tie is not None and tie[0] >= 1 and tie[1] >= 2 and tie[2] >= 2.0 ** -22, (f, cut, tie and tie[:3])
