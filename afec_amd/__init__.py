@@ -17,3 +17,7 @@ from .capi import (  # noqa: F401
     D_CLASSIFICATION_INPUTS, CF_TIME_FRAMES, NUM_CLASSIFICATION_FEATURES, NUM_CF_SILENCE, classification_feature_names,
     D_CLASS_DECISION_INPUTS, DECISION_IS_ONESHOT, DECISION_IS_LOOP, DECISION_OVERRIDDEN, DECISION_SCALARS,
 )
+from .device import (  # noqa: F401
+    DeviceArray, Stream, create_batch_from_device, export, export_into, export_statistics, features, frame_counts,
+    EXPORT_PACKED, EXPORT_PADDED, SERIES, SERIES_MAGNITUDE,
+)

@@ -72,6 +72,14 @@ int first_valid_dtype(const afx_buf* bufs, int32_t n_bufs) {
 // afx_batch_create with the PCM type of the whole call given (afx_extract_batch cuts large calls into groups: the
 // type is decided once, over all buffers, not per group)
 int batch_create_typed(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint32_t mask, int dtype, afx_batch** out_batch) {
+  return batch_create_filled(plan, bufs, n_bufs, mask, dtype, nullptr, nullptr, out_batch);
+}
+
+// ... and with the way the accepted buffers reach the arena given: fill == nullptr is the caller's host memory, one
+// transfer per buffer; afx_device_io.cpp brings a gather launch for device memory.  Which buffers are accepted, their
+// statuses and the dtype rule are decided here, once, for both.
+int batch_create_filled(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint32_t mask, int dtype,
+                        int (*fill)(afx_batch* b, void* ctx), void* fill_ctx, afx_batch** out_batch) {
   if (!plan || !out_batch || n_bufs < 0 || (n_bufs > 0 && !bufs))
     return fail(AFX_ERR_INVALID_ARG, "null argument");
   *out_batch = nullptr;
@@ -94,7 +102,7 @@ int batch_create_typed(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint
   CallerBuffers caller{bufs, n_bufs, (dtype == AFX_PCM_F64) ? (size_t)8 : (size_t)4};
   BatchSource src;
   src.n_bufs = n_bufs; src.mask = mask; src.dtype = dtype; src.lengths = &lengths; src.status = &status;
-  src.fill = fill_from_caller; src.fill_ctx = &caller;
+  src.fill = fill ? fill : fill_from_caller; src.fill_ctx = fill ? fill_ctx : &caller;
   return build_batch(plan, src, out_batch);
 }
 

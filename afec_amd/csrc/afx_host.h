@@ -20,6 +20,9 @@
 //   afx_class_decision.cpp  the fetches that evaluate models on those features: afx_batch_fetch_class_signature (the same
 //                       launch, then gbdt/afx_gbdt.h's), afx_batch_fetch_class_decision (then decide/afx_decide.h's), and
 //                       the two on the caller's own arrays, afx_model_evaluate_features and afx_decide
+//   afx_device_io.cpp   afx_batch_create_from_device, afx_batch_export_device and its two companions: batches from device
+//                       pointers, series into device memory of the caller's; planned in
+//                       devio/afx_devio_plan.h, launchers in devio/afx_devio.h, and none of the files above refers to them
 //   afx_model.cpp       afx_model_create_from_lightgbm / _get_info / _destroy: LightGBM's text into the arrays of
 //                       gbdt/afx_gbdt.h (afx_model.h); no launch
 //
@@ -145,6 +148,8 @@ struct Workspace {
   Buf rt_odf, rt_onsets, rt_scratch, rt_scalars, rt_stats, rt_polar;   // rhythm tracker (its host-filled tables lie in `tables`)
   Buf stat_tmp;                                                                 // half-wave statistics class
   Buf rs_files, rs_groups, rs_ngroups;                                          // sample-rate conversion (afx_resample.hip)
+  Buf devio_in, devio_out;        // device-resident input and output (afx_device_io.cpp): the gather's table; the export's copy of frame_offset
+  hipEvent_t ev_devio = nullptr;  // ... and the event its streams are ordered by (created by the first call that needs it)
   Buf high;                       // the result block of the fetches above a run (afx_block.h: ResultBlock), one at a time: they are synchronous
   void* h_high = nullptr;         // ... and the page-locked host block it lands in (with the call's small inputs on their way up)
   size_t h_high_cap = 0;
@@ -212,6 +217,7 @@ struct afx_batch {
   int64_t* d_frame_offset = nullptr;
   double* d_stats = nullptr;
   double* d_stat_tmp = nullptr;  // half-wave statistics class: raw sums per frame
+  int64_t* d_devio_foff = nullptr;   // afx_device_io.cpp: frame_offset on the device for the padded export, uploaded by the first that needs it
   std::vector<int64_t> arena_off, used;  // per buffer: start and length (samples) of its analysed prefix in d_pcm
   std::vector<double> buf_scale;         // kPcmScaledF32: FinalScaling per buffer (empty otherwise)
   // rhythm tracker (AFX_D_RHYTHM)
@@ -327,6 +333,9 @@ void stamps_report();   // diagnostic build only (make stamps)
 // ---- afx_batch_create.cpp ----
 int first_valid_dtype(const afx_buf* bufs, int32_t n_bufs);
 int batch_create_typed(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint32_t mask, int dtype, afx_batch** out_batch);
+// the same with the arena's fill given (nullptr: transfers from the caller's host memory); afx_device_io.cpp's way in
+int batch_create_filled(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint32_t mask, int dtype,
+                        int (*fill)(afx_batch* b, void* ctx), void* fill_ctx, afx_batch** out_batch);
 
 }  // namespace host
 }  // namespace afx

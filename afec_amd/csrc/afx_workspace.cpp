@@ -16,7 +16,7 @@ namespace host {
 
 std::vector<Workspace::Buf*> Workspace::all_bufs() {
   return {&tables, &pcm, &rec, &mag, &stats, &follower, &efflen, &raw, &files, &scan, &partial, &place, &queue, &rt_polar, &rt_odf,
-          &rt_onsets, &rt_scratch, &rt_scalars, &rt_stats, &stat_tmp, &rs_files, &rs_groups, &rs_ngroups, &high};
+          &rt_onsets, &rt_scratch, &rt_scalars, &rt_stats, &stat_tmp, &rs_files, &rs_groups, &rs_ngroups, &high, &devio_in, &devio_out};
 }
 size_t Workspace::bytes() {
   size_t n = 0;
@@ -35,6 +35,7 @@ void ws_free(Workspace* w) {
   if (w->ev_join) hipEventDestroy(w->ev_join);
   if (w->ev_time_join) hipEventDestroy(w->ev_time_join);
   if (w->ev_copy) hipEventDestroy(w->ev_copy);
+  if (w->ev_devio) hipEventDestroy(w->ev_devio);
   if (w->side_stream) hipStreamDestroy(w->side_stream);
   if (w->stream) hipStreamDestroy(w->stream);
   delete w;

@@ -1,0 +1,323 @@
+"""Device-resident input and output (include/afx.h): batches built from device memory, series exported into
+device memory.  For producers and consumers on the same GPU that this library does not own.
+
+Device memory is reached through the HIP runtime libafx_hip.so itself is linked against (its symbols are resolved through
+the library's handle: no second runtime is loaded).  Anything that exposes __cuda_array_interface__ -- what ROCm builds of
+torch and cupy expose -- can be a source; DeviceArray is the small owner of device memory this module returns.
+"""
+import ctypes
+
+import numpy as np
+
+from . import capi
+
+# series numbers of afx_device_out.series: afx_batch_record_layout's order, then the magnitudes
+SERIES = ["mfcc", "spectral_rms", "spectral_centroid", "spectral_spread", "spectral_skewness", "spectral_kurtosis",
+          "spectral_rolloff", "spectral_flatness", "spectral_flux", "spectrum_bands", "amplitude_peak", "amplitude_rms", "sub_rms",
+          "sub_flatness", "sub_flux", "sub_complexity", "sub_contrast", "spectral_contrast", "amplitude_silence",
+          "amplitude_envelope", "spectral_complexity", "auto_correlation", "f0", "f0_confidence", "failsafe_f0",
+          "spectral_inharmonicity", "tristimulus1", "tristimulus2", "tristimulus3"]
+NUM_SERIES = len(SERIES)
+SERIES_MAGNITUDE = NUM_SERIES
+SERIES_INDEX = {name: i for i, name in enumerate(SERIES + ["magnitude"])}
+SERIES_WIDTH = dict(capi.OUT_FIELDS)
+EXPORT_PACKED, EXPORT_PADDED = 0, 1
+_LAYOUTS = {"packed": EXPORT_PACKED, "padded": EXPORT_PADDED}
+_H2D, _D2H = 1, 2   # hipMemcpyHostToDevice, hipMemcpyDeviceToHost
+
+
+class _DeviceOut(ctypes.Structure):   # afx_device_out
+    _fields_ = [("dst", ctypes.c_void_p), ("series", ctypes.c_int32), ("dtype", ctypes.c_int32), ("row_stride", ctypes.c_int64),
+                ("buf_stride", ctypes.c_int64)]
+
+
+_hip = None
+
+
+def hip():
+    """the HIP runtime's entry points this module uses, found through libafx_hip.so's handle"""
+    global _hip
+    if _hip is None:
+        L = capi.load_library()
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        for name, args in (("hipSetDevice", [ctypes.c_int]), ("hipMalloc", [ctypes.POINTER(vp), sz]), ("hipFree", [vp]),
+                           ("hipMemcpy", [vp, vp, sz, ctypes.c_int]), ("hipMemcpyAsync", [vp, vp, sz, ctypes.c_int, vp]),
+                           ("hipStreamCreate", [ctypes.POINTER(vp)]), ("hipStreamSynchronize", [vp]), ("hipStreamDestroy", [vp])):
+            f = getattr(L, name)
+            f.argtypes, f.restype = args, ctypes.c_int
+        L.hipGetErrorString.restype, L.hipGetErrorString.argtypes = ctypes.c_char_p, [ctypes.c_int]
+        L.afx_batch_create_from_device.argtypes = [vp, ctypes.POINTER(capi._Buf), ctypes.c_int32, ctypes.c_uint32, vp, ctypes.POINTER(vp)]
+        L.afx_batch_export_device.argtypes = [vp, ctypes.POINTER(_DeviceOut), ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                              ctypes.c_double, vp]
+        L.afx_batch_export_statistics_device.argtypes = [vp, ctypes.POINTER(_DeviceOut), ctypes.c_int32, vp]
+        L.afx_batch_export_frame_counts_device.argtypes = [vp, vp, vp]
+        _hip = L
+    return _hip
+
+
+def _hip_check(e, what):
+    if e != 0:
+        raise RuntimeError(f"{what}: HIP error {e} ({(hip().hipGetErrorString(e) or b'').decode()})")
+
+
+class Stream:
+    """a HIP stream of the caller's (hipStreamCreate): what afx_batch_create_from_device and the exports are ordered against"""
+
+    def __init__(self, device=0):
+        H = hip()
+        _hip_check(H.hipSetDevice(device), "hipSetDevice")
+        h = ctypes.c_void_p()
+        _hip_check(H.hipStreamCreate(ctypes.byref(h)), "hipStreamCreate")
+        self.handle = h.value
+
+    def synchronize(self):
+        _hip_check(hip().hipStreamSynchronize(self.handle), "hipStreamSynchronize")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            hip().hipStreamDestroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceArray:
+    """C-contiguous array in device memory: owns its allocation (hipMalloc), or is a view into another DeviceArray's."""
+
+    def __init__(self, shape, dtype, device=0, _base=None, _ptr=None):
+        self.shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+        self.dtype = np.dtype(dtype)
+        self.device = device
+        self.size = int(np.prod(self.shape, dtype=np.int64))
+        self.nbytes = self.size * self.dtype.itemsize
+        self._base = _base
+        if _base is not None:
+            self.ptr = _ptr
+            return
+        self.ptr = None
+        if self.nbytes:
+            H = hip()
+            _hip_check(H.hipSetDevice(device), "hipSetDevice")
+            p = ctypes.c_void_p()
+            _hip_check(H.hipMalloc(ctypes.byref(p), self.nbytes), "hipMalloc")
+            self.ptr = p.value
+
+    @classmethod
+    def from_numpy(cls, a, device=0):
+        a = np.ascontiguousarray(a)
+        d = cls(a.shape, a.dtype, device)
+        d.upload(a)
+        return d
+
+    def view(self, first, shape, dtype=None):
+        """[first, first + prod(shape)) of the flat array as an array of its own (element-aligned, not an owner)"""
+        dtype = np.dtype(dtype or self.dtype)
+        v = DeviceArray(shape, dtype, self.device, _base=self, _ptr=None)
+        if first < 0 or first * self.dtype.itemsize + v.nbytes > self.nbytes:
+            raise ValueError("view beyond the array")
+        v.ptr = (self.ptr or 0) + first * self.dtype.itemsize if v.nbytes else None
+        return v
+
+    def upload(self, a):
+        a = np.ascontiguousarray(a, dtype=self.dtype)
+        if a.size != self.size:
+            raise ValueError("upload of another size than the array's")
+        if self.nbytes:
+            _hip_check(hip().hipSetDevice(self.device), "hipSetDevice")
+            _hip_check(hip().hipMemcpy(self.ptr, a.ctypes.data, self.nbytes, _H2D), "hipMemcpy")
+        return self
+
+    def download(self):
+        out = np.empty(self.shape, dtype=self.dtype)
+        if self.nbytes:
+            _hip_check(hip().hipSetDevice(self.device), "hipSetDevice")
+            _hip_check(hip().hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, _D2H), "hipMemcpy")
+        return out
+
+    def download_async(self, out, stream):
+        """hipMemcpyAsync device-to-host into `out` (C-contiguous, the array's size) on `stream`; nothing is waited for"""
+        if out.nbytes != self.nbytes or not out.flags.c_contiguous:
+            raise ValueError("destination of another size than the array's")
+        if self.nbytes:
+            _hip_check(hip().hipMemcpyAsync(out.ctypes.data, self.ptr, self.nbytes, _D2H, getattr(stream, "handle", stream)), "hipMemcpyAsync")
+
+    @property
+    def __cuda_array_interface__(self):
+        return {"shape": self.shape, "typestr": self.dtype.str, "data": (self.ptr or 0, False), "version": 3, "strides": None}
+
+    def close(self):
+        if self._base is None and getattr(self, "ptr", None):
+            hip().hipFree(self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _stream_handle(stream):
+    return getattr(stream, "handle", stream)
+
+
+def _buffers_of(a, lengths):
+    """an object with __cuda_array_interface__ -> list of (pointer, PCM_*, n_samples)"""
+    if not hasattr(a, "__cuda_array_interface__"):
+        raise TypeError("a source exposes __cuda_array_interface__ (or is a (pointer, dtype code, n_samples) tuple)")
+    cai = a.__cuda_array_interface__
+    dt = np.dtype(cai["typestr"])
+    if dt == np.float32:
+        code = capi.PCM_F32
+    elif dt == np.float64:
+        code = capi.PCM_F64
+    else:
+        raise TypeError("PCM buffers must be float32 or float64")
+    shape, strides, ptr = tuple(cai["shape"]), cai.get("strides"), cai["data"][0]
+    if strides is None:
+        strides = tuple(int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape)))
+    if len(shape) not in (1, 2) or (shape[-1] > 1 and strides[-1] != dt.itemsize):
+        raise ValueError("a source is 1-D or 2-D [n, max_len] and contiguous in its last dimension")
+    if len(shape) == 1:
+        if lengths is not None:
+            raise ValueError("lengths go with a 2-D [n, max_len] source")
+        return [(ptr if shape[0] else None, code, shape[0])]
+    if lengths is None or len(lengths) != shape[0]:
+        raise ValueError("a 2-D [n, max_len] source needs one length per row")
+    if strides[0] < 0 or strides[0] % dt.itemsize or any(int(n) > shape[1] for n in lengths):
+        raise ValueError("a row of a 2-D source holds at most max_len samples, rows an element multiple apart")
+    return [(ptr + i * strides[0] if int(n) > 0 else None, code, int(n)) for i, n in enumerate(lengths)]
+
+
+def create_batch_from_device(plan, arrays, mask=capi.D_ALL_LOW_LEVEL, lengths=None, stream=None):
+    """afx_batch_create_from_device -> capi.Batch.  arrays: a list of 1-D device arrays (anything with
+    __cuda_array_interface__, float32 or float64, last dimension contiguous) or of (pointer, PCM_* code, n_samples) tuples as
+    the C call takes them, or ONE 2-D [n, max_len] array with `lengths` (one per row).  stream: the producer's (a Stream or
+    a hipStream_t as an int; None: the null stream).  Synchronous: the sources may be freed on return."""
+    if hasattr(arrays, "__cuda_array_interface__"):
+        specs = _buffers_of(arrays, lengths)
+    else:
+        if lengths is not None:
+            raise ValueError("lengths go with a 2-D [n, max_len] source")
+        specs = []
+        for a in arrays:
+            specs += [tuple(a)] if isinstance(a, (tuple, list)) else _buffers_of(a, None)
+    H = hip()
+    n = len(specs)
+    arr = (capi._Buf * max(1, n))()
+    for i, (ptr, code, count) in enumerate(specs):
+        arr[i].pcm, arr[i].dtype, arr[i].n_samples = ptr or None, code, count
+    h = ctypes.c_void_p()
+    capi._check(H, H.afx_batch_create_from_device(plan.h, arr, n, mask, _stream_handle(stream), ctypes.byref(h)))
+    b = capi.Batch.__new__(capi.Batch)
+    b.plan, b.L, b.mask, b.n_bufs, b.h = plan, H, mask, n, h
+    b.total_frames = int(H.afx_batch_total_frames(h))
+    return b
+
+
+def frame_offsets(batch):
+    """frame_offset [n_bufs + 1] and buf_status [n_bufs] of a batch that has run (host arrays)"""
+    out = capi._Out()
+    fo, bs = np.zeros(batch.n_bufs + 1, dtype=np.int64), np.zeros(max(1, batch.n_bufs), dtype=np.int32)
+    out.frame_offset, out.buf_status = fo.ctypes.data, bs.ctypes.data
+    capi._check(batch.L, batch.L.afx_batch_fetch(batch.h, ctypes.byref(out)))
+    return fo, bs[:batch.n_bufs]
+
+
+def _dtype_code(dtype):
+    dtype = np.dtype(dtype)
+    if dtype == np.float64:
+        return capi.PCM_F64
+    if dtype == np.float32:
+        return capi.PCM_F32
+    raise TypeError("an export is float64 or float32")
+
+
+def export_into(batch, outs, layout=EXPORT_PADDED, max_frames=0, pad=0.0, stream=None):
+    """afx_batch_export_device as the C call takes it.  outs: list of (destination, series number, PCM_* code, row_stride,
+    buf_stride); a destination is a DeviceArray (or anything with __cuda_array_interface__) or a pointer."""
+    H = hip()
+    arr = (_DeviceOut * max(1, len(outs)))()
+    for k, (dst, series, code, row_stride, buf_stride) in enumerate(outs):
+        ptr = dst.__cuda_array_interface__["data"][0] if hasattr(dst, "__cuda_array_interface__") else dst
+        arr[k].dst, arr[k].series, arr[k].dtype, arr[k].row_stride, arr[k].buf_stride = ptr or None, series, code, row_stride, buf_stride
+    capi._check(H, H.afx_batch_export_device(batch.h, arr, len(outs), layout, max_frames, pad, _stream_handle(stream)))
+
+
+def _series_numbers(series):
+    return [SERIES_INDEX[s] if isinstance(s, str) else int(s) for s in series]
+
+
+def _width(number):
+    return 1024 if number == SERIES_MAGNITUDE else SERIES_WIDTH[SERIES[number]]
+
+
+def export(batch, series, layout="padded", dtype=np.float64, pad=0.0, stream=None, max_frames=None):
+    """Chosen series of a batch that has run, each into a new DeviceArray, by ONE afx_batch_export_device call -> dict by
+    series name: [F, W] packed, [n_bufs, max_frames, W] padded (W left out for scalar series); rows at and behind a file's
+    frame count hold `pad`.  max_frames: the longest file's frames unless given.  stream: the consumer's (the call then does
+    not wait on the host); None: the data is there on return."""
+    code, numbers = _dtype_code(dtype), _series_numbers(series)
+    fo, _ = frame_offsets(batch)
+    counts = np.diff(fo)
+    if max_frames is None:
+        max_frames = int(counts.max()) if counts.size else 0
+    padded = _LAYOUTS[layout] == EXPORT_PADDED
+    res, outs = {}, []
+    for s in numbers:
+        w = _width(s)
+        lead = (batch.n_bufs, max_frames) if padded else (int(fo[-1]),)
+        a = DeviceArray(lead + ((w,) if w > 1 else ()), dtype)
+        res[(SERIES + ["magnitude"])[s]] = a
+        outs.append((a.ptr or 1, s, code, w, max_frames * w))   # (an empty destination: any non-null pointer, nothing is written)
+    export_into(batch, outs, _LAYOUTS[layout], max_frames if padded else 0, pad, stream)
+    return res
+
+
+def features(batch, series, dtype=np.float32, pad=0.0, stream=None, max_frames=None):
+    """The chosen series side by side as ONE [n_bufs, max_frames, sum of widths] DeviceArray, filled by a single
+    afx_batch_export_device call whose destinations are column slices of it (row_stride = the sum of the widths).
+    The array's `columns` says where each series lies: {series name: (first column, width)}."""
+    code, numbers = _dtype_code(dtype), _series_numbers(series)
+    fo, _ = frame_offsets(batch)
+    counts = np.diff(fo)
+    if max_frames is None:
+        max_frames = int(counts.max()) if counts.size else 0
+    total = sum(_width(s) for s in numbers)
+    a = DeviceArray((batch.n_bufs, max_frames, total), dtype)
+    outs, columns, col = [], {}, 0
+    for s in numbers:
+        w = _width(s)
+        outs.append((a.ptr + col * a.dtype.itemsize if a.ptr else 1, s, code, total, max_frames * total))
+        columns[(SERIES + ["magnitude"])[s]] = (col, w)
+        col += w
+    export_into(batch, outs, EXPORT_PADDED, max_frames, pad, stream)
+    a.columns = columns
+    return a
+
+
+def export_statistics(batch, series, dtype=np.float64, stream=None):
+    """afx_batch_export_statistics_device -> dict by series name of DeviceArray [n_bufs, W, 13] (W left out for scalar series)"""
+    H = hip()
+    code, numbers = _dtype_code(dtype), _series_numbers(series)
+    arr = (_DeviceOut * max(1, len(numbers)))()
+    res = {}
+    for k, s in enumerate(numbers):
+        w = _width(s) if s != SERIES_MAGNITUDE else 1
+        a = DeviceArray((batch.n_bufs,) + ((w,) if w > 1 else ()) + (capi.NUM_STATISTICS,), dtype)
+        res[(SERIES + ["magnitude"])[s]] = a
+        arr[k].dst, arr[k].series, arr[k].dtype = a.ptr or 1, s, code
+    capi._check(H, H.afx_batch_export_statistics_device(batch.h, arr, len(numbers), _stream_handle(stream)))
+    return res
+
+
+def frame_counts(batch, stream=None):
+    """afx_batch_export_frame_counts_device -> DeviceArray int64 [n_bufs]"""
+    H = hip()
+    a = DeviceArray((batch.n_bufs,), np.int64)
+    capi._check(H, H.afx_batch_export_frame_counts_device(batch.h, a.ptr, _stream_handle(stream)))
+    return a

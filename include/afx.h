@@ -153,7 +153,7 @@ int64_t afx_num_frames(const afx_plan* plan, int64_t n_samples);
 
 /* ---- input / output ---- */
 typedef struct {
-  const void* pcm;   /* host pointer, mono, AFX_PCM_* */
+  const void* pcm;   /* host pointer (a device pointer for afx_batch_create_from_device), mono, AFX_PCM_* */
   int32_t dtype;
   int32_t reserved;
   int64_t n_samples;
@@ -294,6 +294,57 @@ int afx_batch_record_layout(const afx_batch* batch, int32_t* stride, int32_t* of
                             int32_t* widths /* [AFX_NUM_SERIES] */);
 int afx_batch_fetch_records(afx_batch* batch, double* records, double* statistics, int64_t* frame_offset /* [n_bufs+1] */,
                             int32_t* buf_status /* [n_bufs] */, double* effective_length /* [n_bufs][3] or NULL */);
+
+/* ---- device-resident input and output ----
+ * For a consumer or producer on the same GPU that the library does not own (a model, an index, a decoder that has left
+ * PCM in HBM): a batch built from device pointers, and chosen series of its records written straight into device memory
+ * of the caller's.  Additive: every other entry point launches what it launched before.
+ *
+ * afx_batch_create_from_device is afx_batch_create with afx_buf.pcm a DEVICE pointer on the plan's device.  Synchronous
+ * like it: the library records an event on producer_stream (NULL: the null stream), makes the batch's stream wait for
+ * it, copies every buffer's analysed prefix into the batch's arena with one gather launch and waits for that, so the
+ * caller may free or reuse the source on return.  The results are bit-identical to those of afx_batch_create on the
+ * same samples.  Statuses, the dtype rule (the first valid buffer decides, others get AFX_ERR_BAD_BUFFER), n_bufs == 0
+ * and zero-length buffers are afx_batch_create's.  In addition the range [pcm, pcm + n_samples * element size) of every
+ * non-empty buffer must lie inside ONE device allocation on the plan's device: a host pointer, a pointer of another
+ * device or a range that leaves its allocation gets that buffer AFX_ERR_BAD_BUFFER before anything is enqueued (and such
+ * a buffer does not decide the dtype).  A slice of a larger allocation is fine and need only be element-aligned. */
+int afx_batch_create_from_device(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint32_t mask,
+                                 void* producer_stream /* hipStream_t */, afx_batch** out_batch);
+
+/* One destination of an export.  Series are numbered in afx_batch_record_layout's order; AFX_SERIES_MAGNITUDE is the
+ * stored magnitude spectrum, [F][1024] (AFX_D_MAGNITUDE). */
+#define AFX_SERIES_MAGNITUDE AFX_NUM_SERIES
+typedef struct {
+  void*   dst;        /* device pointer on the plan's device */
+  int32_t series;     /* 0 .. AFX_NUM_SERIES - 1, or AFX_SERIES_MAGNITUDE */
+  int32_t dtype;      /* AFX_PCM_F64: the records' bits; AFX_PCM_F32: (float) of them, round to nearest even */
+  int64_t row_stride; /* elements between consecutive frames, >= the series' width: a column slice of a wider tensor */
+  int64_t buf_stride; /* AFX_EXPORT_PADDED: elements between files; ignored when packed */
+} afx_device_out;
+enum {
+  AFX_EXPORT_PACKED = 0, /* rows as in afx_out: [F][row_stride], frames of file i at rows frame_offset[i] .. */
+  AFX_EXPORT_PADDED = 1  /* [n_bufs][max_frames][row_stride]: rows at and behind a file's frame count get pad_value */
+};
+/* After afx_batch_run, any number of times.  ONE launch covers all outs of a call (at most AFX_NUM_SERIES + 1); it is
+ * enqueued on the batch's stream behind the run.  consumer_stream (a hipStream_t) non-NULL: that stream is made to wait
+ * for the launch and the call returns without waiting on the host; NULL: the call returns when the data is there.
+ * Of every row only the series' width is written: the elements between it and row_stride are not touched.  pad_value is
+ * written with its bits as a double ((float) of it into a float destination), so -0.0 and NaN survive.  Refused and
+ * empty files own zero rows (all padding when padded).  Destinations that overlap are the caller's business: which
+ * write lands last is not defined.
+ * AFX_ERR_INVALID_ARG, with nothing enqueued: before the first run; more than AFX_NUM_SERIES + 1 outs; a series that is
+ * not in the batch mask; a row_stride below the series' width; padded: max_frames below the longest file's frames or a
+ * buf_stride below max_frames x row_stride; a dtype or layout that is neither of the two; a NULL dst; a destination
+ * whose extent -- (F - 1) x row_stride + width elements packed, (n_bufs - 1) x buf_stride + (max_frames - 1) x
+ * row_stride + width padded -- overflows or does not lie inside ONE device allocation on the plan's device. */
+int afx_batch_export_device(afx_batch* batch, const afx_device_out* outs, int32_t n_outs, int32_t layout,
+                            int64_t max_frames, double pad_value, void* consumer_stream);
+/* The per-file statistics (AFX_D_STATISTICS) of the chosen series, [n_bufs][W][AFX_NUM_STATISTICS] each as
+ * afx_batch_fetch_statistics lays them out; row_stride / buf_stride are unused, AFX_SERIES_MAGNITUDE has none. */
+int afx_batch_export_statistics_device(afx_batch* batch, const afx_device_out* outs, int32_t n_outs, void* consumer_stream);
+/* frames of every file, frame_offset[i + 1] - frame_offset[i]: the lengths that go with a padded export */
+int afx_batch_export_frame_counts_device(afx_batch* batch, int64_t* d_counts /* [n_bufs], device */, void* consumer_stream);
 
 /* ---- LoadSample front end: TSampleAnalyser::LoadSample, SampleAnalyser.cpp:484-718 ---- *
  * Decoded, interleaved PCM of a file in; on the GPU: conversion to the reference's "16-bit float"
