@@ -158,7 +158,7 @@ hipError_t send_file_tables(RawBatch& r) {
 // run and goes through the plan's upload stream; otherwise one transfer per run (each costs ~10 us of runtime overhead,
 // which dominates for thousands of short files).  Only bytes of accepted buffers are read: what lies behind a buffer, or
 // in a refused one, is not the library's to read (a buffer may end at the end of a mapping).
-hipError_t upload_pieces(RawBatch& r) {
+hipError_t upload_pieces(RawBatch& r, void*) {
   std::vector<RawPlan::Piece> runs;
   for (const RawPlan::Piece& p : r.pieces) {
     if (!runs.empty()) {
@@ -220,15 +220,22 @@ hipError_t scan_files(RawBatch& r) {
   return hipMemcpyAsync((unsigned char*)r.ws->h_pin + r.pin.scan_off, d_scan, r.pin.scan_bytes, hipMemcpyDeviceToHost, r.ws->stream);
 }
 
-// upload and tables -> (FLAC decode) -> (byte order) -> (conversion) -> scan -> results on the host, with one wait
-hipError_t stage_and_scan(RawBatch& r, const char** what) {
+// what a caller brings in upload_pieces' place (afx_host.h: RawMove)
+hipError_t move_by_caller(RawBatch& r, void* ctx) {
+  const RawMoveStep& step = *(const RawMoveStep*)ctx;
+  return step.move(r, r.plan, r.ws, r.d_raw, step.ctx);
+}
+
+// upload and tables -> (FLAC decode) -> (byte order) -> (conversion) -> scan -> results on the host, with one wait.
+// move_pieces is the one step that touches the caller's memory: upload_pieces, or the caller's own
+hipError_t stage_and_scan(RawBatch& r, const char** what, hipError_t (*move_pieces)(RawBatch&, void*), void* move_ctx) {
   hipError_t e;
   *what = "hipMalloc(raw staging)";
   if ((e = reserve_buffers(r)) != hipSuccess) return e;
   *what = "flac_decode";
   if ((e = send_flac_table(r)) != hipSuccess) return e;
   *what = "hipMemcpy(raw)";
-  if ((e = upload_pieces(r)) != hipSuccess) return e;
+  if ((e = move_pieces(r, move_ctx)) != hipSuccess) return e;
   *what = "hipMemcpy(tables)";
   if ((e = send_file_tables(r)) != hipSuccess) return e;
   *what = "flac_decode";
@@ -297,32 +304,12 @@ int fill_from_staging(afx_batch* b, void* ctx) {
 
 }  // namespace
 
-}  // namespace host
-}  // namespace afx
-
-using namespace afx::host;
-
-extern "C" {
-
-int afx_batch_create(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint32_t mask,
-                     afx_batch** out_batch) {
-  if (!plan || !out_batch || n_bufs < 0 || (n_bufs > 0 && !bufs))
-    return fail(AFX_ERR_INVALID_ARG, "null argument");
-  return batch_create_typed(plan, bufs, n_bufs, mask, first_valid_dtype(bufs, n_bufs), out_batch);
-}
-
-// LoadSample front end (SampleAnalyser.cpp:484-718) on the GPU: decoded interleaved PCM in,
-// peak-normalised, silence-trimmed, padded mono signal in the analysis arena out.
-int afx_batch_create_from_raw(afx_plan* plan, const afx_raw* raws, int32_t n_bufs, uint32_t mask,
-                              afx_batch** out_batch, afx_load_info* info) {
-  if (!plan || !out_batch || n_bufs < 0 || (n_bufs > 0 && !raws))
-    return fail(AFX_ERR_INVALID_ARG, "null argument");
-  *out_batch = nullptr;
-  if (!mask_ok(mask)) return fail(AFX_ERR_INVALID_ARG, "bad descriptor mask");
-  HIP_TRY(hipSetDevice(plan->desc.device));
-
-  // the launchers a build lacks (weak references, above) decide what the plan refuses
-  RawBatch r{plan_raw_arena(raws, n_bufs, plan->desc.sample_rate, afx::launch_raw_native != nullptr, afx::launch_flac_decode != nullptr), plan};
+// afx_batch_create_from_raw behind its plan: `planned` is plan_raw_arena's record of `raws`; move == nullptr is the
+// caller's host memory (upload_pieces); afx_device_io.cpp brings a gather launch for device memory.
+int batch_create_from_raw_plan(afx_plan* plan, RawPlan&& planned, const afx_raw* raws, uint32_t mask, RawMove move, void* move_ctx,
+                               afx_batch** out_batch, afx_load_info* info) {
+  const int32_t n_bufs = planned.n_bufs;
+  RawBatch r{std::move(planned), plan};
   r.scan.resize((size_t)n_bufs);
   r.place.resize((size_t)n_bufs);
   r.lengths.assign((size_t)n_bufs, 0);
@@ -334,7 +321,8 @@ int afx_batch_create_from_raw(afx_plan* plan, const afx_raw* raws, int32_t n_buf
   if (!r.ws) return hip_fail(e, "workspace");
   if (n_bufs > 0) {
     const char* what = "";
-    if ((e = stage_and_scan(r, &what)) != hipSuccess) {
+    RawMoveStep step{move, move_ctx};
+    if ((e = move ? stage_and_scan(r, &what, move_by_caller, &step) : stage_and_scan(r, &what, upload_pieces, nullptr)) != hipSuccess) {
       ws_release(plan, r.ws);
       return hip_fail(e, what);
     }
@@ -368,6 +356,36 @@ int afx_batch_create_from_raw(afx_plan* plan, const afx_raw* raws, int32_t n_buf
     g_create_timing.ns[2] += t_end - t_placed; g_create_timing.ns[3] += 1;
   }
   return st;
+}
+
+}  // namespace host
+}  // namespace afx
+
+using namespace afx::host;
+
+extern "C" {
+
+int afx_batch_create(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint32_t mask,
+                     afx_batch** out_batch) {
+  if (!plan || !out_batch || n_bufs < 0 || (n_bufs > 0 && !bufs))
+    return fail(AFX_ERR_INVALID_ARG, "null argument");
+  return batch_create_typed(plan, bufs, n_bufs, mask, first_valid_dtype(bufs, n_bufs), out_batch);
+}
+
+// LoadSample front end (SampleAnalyser.cpp:484-718) on the GPU: decoded interleaved PCM in,
+// peak-normalised, silence-trimmed, padded mono signal in the analysis arena out.
+int afx_batch_create_from_raw(afx_plan* plan, const afx_raw* raws, int32_t n_bufs, uint32_t mask,
+                              afx_batch** out_batch, afx_load_info* info) {
+  if (!plan || !out_batch || n_bufs < 0 || (n_bufs > 0 && !raws))
+    return fail(AFX_ERR_INVALID_ARG, "null argument");
+  *out_batch = nullptr;
+  if (!mask_ok(mask)) return fail(AFX_ERR_INVALID_ARG, "bad descriptor mask");
+  HIP_TRY(hipSetDevice(plan->desc.device));
+
+  // the launchers a build lacks (weak references, above) decide what the plan refuses
+  return batch_create_from_raw_plan(plan, plan_raw_arena(raws, n_bufs, plan->desc.sample_rate, afx::launch_raw_native != nullptr,
+                                                         afx::launch_flac_decode != nullptr),
+                                    raws, mask, nullptr, nullptr, out_batch, info);
 }
 
 int afx_extract_batch(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint32_t mask, afx_out* out) {

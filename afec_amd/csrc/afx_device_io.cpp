@@ -1,14 +1,22 @@
 // afec_amd/csrc/afx_device_io.cpp -- device-resident input and output: a batch from device pointers
 // (afx_batch_create_from_device: afx_batch_create's rules, one gather launch in place of its transfers) and chosen series
-// of a batch's records into device memory of the caller's (afx_batch_export_device and its two companions).  Everything is
-// decided by devio/afx_devio_plan.h before anything is enqueued; here the runtime is asked what the caller's pointers
-// are, and the record is enqueued.  See afx_host.h for the map of the host side.
+// of a batch's records into device memory of the caller's (afx_batch_export_device and its two companions); and (DESIGN
+// 4.21) LoadSample on raw PCM in device memory (afx_batch_create_from_raw_device: afx_batch_create_from_raw's plan and
+// steps, one gather launch in place of its transfers) and the analysed samples into device memory
+// (afx_batch_export_samples_device, afx_batch_export_sample_counts_device).  Everything is decided by
+// devio/afx_devio_plan.h and devio/afx_devio_raw_plan.h before anything is enqueued; here the runtime is asked what the
+// caller's pointers are, and the record is enqueued.  See afx_host.h for the map of the host side.
 
+#include <cstdlib>
+#include <cstring>
+#include <utility>
 #include <vector>
 
 #include "afx_host.h"
 #include "devio/afx_devio.h"
 #include "devio/afx_devio_plan.h"
+#include "devio/afx_devio_raw.h"
+#include "devio/afx_devio_raw_plan.h"
 
 using namespace afx::host;
 
@@ -100,6 +108,44 @@ int device_frame_offsets(afx_batch* b) {
   return AFX_OK;
 }
 
+struct RawDeviceBuffers {   // RawMove of afx_batch_create_from_raw_device: one gather launch in place of the transfers
+  hipStream_t producer;
+  const RawGatherPlan* gather;   // lives until the create has waited for its scan
+  int elementwise;
+};
+hipError_t gather_raw(const RawPlan&, afx_plan* plan, Workspace* ws, unsigned char* d_raw, void* ctx) {
+  const RawDeviceBuffers& c = *(const RawDeviceBuffers*)ctx;
+  if (c.gather->table.empty()) return hipSuccess;
+  const size_t bytes = c.gather->table.size() * sizeof(afx::DevioRawBuf);
+  hipError_t e;
+  if ((e = ws_reserve(plan, ws->devio_in, bytes)) != hipSuccess) return e;
+  // what the producer has enqueued so far is in front of the gather
+  if ((e = devio_event(ws)) != hipSuccess) return e;
+  if ((e = hipEventRecord(ws->ev_devio, c.producer)) != hipSuccess) return e;
+  if ((e = hipStreamWaitEvent(ws->stream, ws->ev_devio, 0)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(ws->devio_in.p, c.gather->table.data(), bytes, hipMemcpyHostToDevice, ws->stream)) != hipSuccess) return e;
+  return afx::launch_devio_raw_gather(d_raw, (const afx::DevioRawBuf*)ws->devio_in.p, (int)c.gather->table.size(), c.gather->tiles,
+                                      c.elementwise, ws->stream);
+}
+
+// arena_off, used and the scalings on the device, uploaded once per batch behind whatever its stream holds
+int device_sample_rows(afx_batch* b) {
+  if (b->d_devio_rows || b->n_bufs == 0) return AFX_OK;
+  const size_t n = (size_t)b->n_bufs;
+  b->h_devio_rows.assign(3 * n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const double scale = b->pcm_dtype == afx::kPcmScaledF32 ? b->buf_scale[i] : 1.0;
+    b->h_devio_rows[i] = b->arena_off[i];
+    b->h_devio_rows[n + i] = b->used[i];
+    std::memcpy(&b->h_devio_rows[2 * n + i], &scale, sizeof(double));
+  }
+  const size_t bytes = 3 * n * sizeof(int64_t);
+  HIP_TRY(ws_reserve(b->plan, b->ws->devio_rows, bytes));
+  HIP_TRY(hipMemcpyAsync(b->ws->devio_rows.p, b->h_devio_rows.data(), bytes, hipMemcpyHostToDevice, b->stream));
+  b->d_devio_rows = (int64_t*)b->ws->devio_rows.p;
+  return AFX_OK;
+}
+
 // the consumer's stream behind the launch, or the host
 int hand_over(afx_batch* b, void* consumer_stream) {
   if (!consumer_stream) {
@@ -177,6 +223,61 @@ int afx_batch_export_frame_counts_device(afx_batch* b, int64_t* d_counts, void* 
     const int st = device_frame_offsets(b);
     if (st != AFX_OK) return st;
     HIP_TRY(afx::launch_devio_frame_counts(b->d_devio_foff, b->n_bufs, d_counts, b->stream));
+  }
+  return hand_over(b, consumer_stream);
+}
+
+int afx_batch_create_from_raw_device(afx_plan* plan, const afx_raw_device* raws, int32_t n_bufs, uint32_t mask, void* producer_stream,
+                                     afx_batch** out_batch, afx_load_info* info) {
+  if (!plan || !out_batch || n_bufs < 0 || (n_bufs > 0 && !raws))
+    return fail(AFX_ERR_INVALID_ARG, "null argument");
+  *out_batch = nullptr;
+  if (!mask_ok(mask)) return fail(AFX_ERR_INVALID_ARG, "bad descriptor mask");
+  HIP_TRY(hipSetDevice(plan->desc.device));
+  std::vector<DevioAlloc> allocs((size_t)n_bufs);
+  for (int32_t i = 0; i < n_bufs; ++i)
+    if (devio_raw_is_read(raws[i])) allocs[(size_t)i] = ask_runtime(raws[i].data);
+  const std::vector<afx_raw> checked = devio_raw_checked(raws, allocs.data(), n_bufs, plan->desc.device);
+  // afx_batch_create_from_raw's plan of the same buffers, made without the FLAC decoder: a stream's descriptor would be
+  // read on the host
+  RawPlan planned = plan_raw_arena(checked.data(), n_bufs, plan->desc.sample_rate, true, false);
+  const RawGatherPlan gather = plan_raw_gather(planned, raws);
+  if (!gather.ok) return fail(AFX_ERR_INVALID_ARG, "more sample frames than one gather launch covers");
+  // AFX_DEVIO_RAW_ELEMENTWISE in the environment: misaligned interleaved buffers element by element (diagnostic, for
+  // tools/devio_raw_cost.py's comparison of the two forms)
+  static const int elementwise = std::getenv("AFX_DEVIO_RAW_ELEMENTWISE") != nullptr;
+  RawDeviceBuffers ctx{(hipStream_t)producer_stream, &gather, elementwise};
+  return batch_create_from_raw_plan(plan, std::move(planned), checked.data(), mask, gather_raw, &ctx, out_batch, info);
+}
+
+int afx_batch_export_samples_device(afx_batch* b, void* dst, int32_t dtype, int64_t buf_stride, double pad_value, void* consumer_stream) {
+  if (!b) return fail(AFX_ERR_INVALID_ARG, "null batch");
+  const SamplesExportPlan p = plan_export_samples(b->used.data(), b->n_bufs, dst, dtype, buf_stride);
+  if (p.status != AFX_OK) return fail(p.status, p.why);
+  HIP_TRY(hipSetDevice(b->plan->desc.device));
+  if (p.extent_bytes > 0) {
+    if (!devio_range_ok(ask_runtime(dst), b->plan->desc.device, dst, p.extent_bytes))
+      return fail(AFX_ERR_INVALID_ARG, "the destination's extent does not lie inside one device allocation on the plan's device");
+    const int st = device_sample_rows(b);
+    if (st != AFX_OK) return st;
+    afx::DevioSamplesArgs a{};
+    a.pcm = b->d_pcm; a.rows = b->d_devio_rows; a.dst = dst; a.buf_stride = buf_stride; a.pad_value = pad_value;
+    a.n_bufs = b->n_bufs; a.pcm_kind = b->pcm_dtype; a.f32 = p.f32; a.tiles_per_row = p.tiles_per_row;
+    HIP_TRY(afx::launch_devio_samples(a, b->stream));
+  }
+  return hand_over(b, consumer_stream);
+}
+
+int afx_batch_export_sample_counts_device(afx_batch* b, int64_t* d_counts, void* consumer_stream) {
+  if (!b) return fail(AFX_ERR_INVALID_ARG, "null batch");
+  if (b->n_bufs > 0 && !d_counts) return fail(AFX_ERR_INVALID_ARG, "null destination");
+  HIP_TRY(hipSetDevice(b->plan->desc.device));
+  if (b->n_bufs > 0) {
+    if (!devio_range_ok(ask_runtime(d_counts), b->plan->desc.device, d_counts, (uint64_t)b->n_bufs * sizeof(int64_t)))
+      return fail(AFX_ERR_INVALID_ARG, "the destination does not lie inside one device allocation on the plan's device");
+    const int st = device_sample_rows(b);
+    if (st != AFX_OK) return st;
+    HIP_TRY(afx::launch_devio_sample_counts(b->d_devio_rows, b->n_bufs, d_counts, b->stream));
   }
   return hand_over(b, consumer_stream);
 }

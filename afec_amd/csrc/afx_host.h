@@ -22,7 +22,10 @@
 //                       the two on the caller's own arrays, afx_model_evaluate_features and afx_decide
 //   afx_device_io.cpp   afx_batch_create_from_device, afx_batch_export_device and its two companions: batches from device
 //                       pointers, series into device memory of the caller's; planned in
-//                       devio/afx_devio_plan.h, launchers in devio/afx_devio.h, and none of the files above refers to them
+//                       devio/afx_devio_plan.h, launchers in devio/afx_devio.h, and none of the files above refers to them;
+//                       afx_batch_create_from_raw_device (afx_batch_create_from_raw's plan and steps behind one gather
+//                       launch: batch_create_from_raw_plan below), afx_batch_export_samples_device and its companion
+//                       (DESIGN 4.21); planned in devio/afx_devio_raw_plan.h, launchers in devio/afx_devio_raw.h
 //   afx_model.cpp       afx_model_create_from_lightgbm / _get_info / _destroy: LightGBM's text into the arrays of
 //                       gbdt/afx_gbdt.h (afx_model.h); no launch
 //
@@ -149,6 +152,7 @@ struct Workspace {
   Buf stat_tmp;                                                                 // half-wave statistics class
   Buf rs_files, rs_groups, rs_ngroups;                                          // sample-rate conversion (afx_resample.hip)
   Buf devio_in, devio_out;        // device-resident input and output (afx_device_io.cpp): the gather's table; the export's copy of frame_offset
+  Buf devio_rows;                 // ... the sample export's copy of arena_off, used and the scalings
   hipEvent_t ev_devio = nullptr;  // ... and the event its streams are ordered by (created by the first call that needs it)
   Buf high;                       // the result block of the fetches above a run (afx_block.h: ResultBlock), one at a time: they are synchronous
   void* h_high = nullptr;         // ... and the page-locked host block it lands in (with the call's small inputs on their way up)
@@ -218,6 +222,8 @@ struct afx_batch {
   double* d_stats = nullptr;
   double* d_stat_tmp = nullptr;  // half-wave statistics class: raw sums per frame
   int64_t* d_devio_foff = nullptr;   // afx_device_io.cpp: frame_offset on the device for the padded export, uploaded by the first that needs it
+  int64_t* d_devio_rows = nullptr;   // afx_device_io.cpp: [3][n_bufs] arena_off, used, the scalings' bits for the sample export, likewise
+  std::vector<int64_t> h_devio_rows; // ... and the host copy the upload reads
   std::vector<int64_t> arena_off, used;  // per buffer: start and length (samples) of its analysed prefix in d_pcm
   std::vector<double> buf_scale;         // kPcmScaledF32: FinalScaling per buffer (empty otherwise)
   // rhythm tracker (AFX_D_RHYTHM)
@@ -336,6 +342,14 @@ int batch_create_typed(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint
 // the same with the arena's fill given (nullptr: transfers from the caller's host memory); afx_device_io.cpp's way in
 int batch_create_filled(afx_plan* plan, const afx_buf* bufs, int32_t n_bufs, uint32_t mask, int dtype,
                         int (*fill)(afx_batch* b, void* ctx), void* fill_ctx, afx_batch** out_batch);
+// afx_batch_create_from_raw behind its plan (afx_raw_plan.h: plan_raw_arena's record of `raws`), with the one step that
+// touches the caller's memory given: RawMove puts RawPlan::pieces into the raw arena at d_raw, on ws->stream or waited
+// for (nullptr: transfers from the caller's host memory).  afx_device_io.cpp's way in for raw PCM in device memory.
+struct RawPlan;
+typedef hipError_t (*RawMove)(const RawPlan& planned, afx_plan* plan, Workspace* ws, unsigned char* d_raw, void* ctx);
+struct RawMoveStep { RawMove move; void* ctx; };
+int batch_create_from_raw_plan(afx_plan* plan, RawPlan&& planned, const afx_raw* raws, uint32_t mask, RawMove move, void* move_ctx,
+                               afx_batch** out_batch, afx_load_info* info);
 
 }  // namespace host
 }  // namespace afx

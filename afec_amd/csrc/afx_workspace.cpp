@@ -16,7 +16,8 @@ namespace host {
 
 std::vector<Workspace::Buf*> Workspace::all_bufs() {
   return {&tables, &pcm, &rec, &mag, &stats, &follower, &efflen, &raw, &files, &scan, &partial, &place, &queue, &rt_polar, &rt_odf,
-          &rt_onsets, &rt_scratch, &rt_scalars, &rt_stats, &stat_tmp, &rs_files, &rs_groups, &rs_ngroups, &high, &devio_in, &devio_out};
+          &rt_onsets, &rt_scratch, &rt_scalars, &rt_stats, &stat_tmp, &rs_files, &rs_groups, &rs_ngroups, &high, &devio_in, &devio_out,
+          &devio_rows};
 }
 size_t Workspace::bytes() {
   size_t n = 0;

@@ -1,5 +1,6 @@
-"""Device-resident input and output (include/afx.h): batches built from device memory, series exported into
-device memory.  For producers and consumers on the same GPU that this library does not own.
+"""Device-resident input and output (include/afx.h): batches built from device memory -- normalised mono
+buffers, or raw PCM through the LoadSample front end --, series and the analysed samples exported into device memory.  For
+producers and consumers on the same GPU that this library does not own.
 
 Device memory is reached through the HIP runtime libafx_hip.so itself is linked against (its symbols are resolved through
 the library's handle: no second runtime is loaded).  Anything that exposes __cuda_array_interface__ -- what ROCm builds of
@@ -31,6 +32,17 @@ class _DeviceOut(ctypes.Structure):   # afx_device_out
                 ("buf_stride", ctypes.c_int64)]
 
 
+class _RawDevice(ctypes.Structure):   # afx_raw_device
+    _fields_ = [("data", ctypes.c_void_p), ("format", ctypes.c_int32), ("channels", ctypes.c_int32), ("sample_rate", ctypes.c_int32),
+                ("layout", ctypes.c_int32), ("n_frames", ctypes.c_int64), ("channel_stride", ctypes.c_int64)]
+
+
+RAW_INTERLEAVED, RAW_PLANAR = 0, 1
+RAW_TILE_FRAMES = 2048   # kDevioRawTileFrames (csrc/devio/afx_devio_raw.h): sample frames one workgroup of the gather moves
+SAMPLE_TILE = 4096       # kDevioSampleTile: elements of a row one workgroup of the sample export writes
+_RAW_FORMAT = {np.dtype(np.int16): capi.RAW_I16, np.dtype(np.int32): capi.RAW_I32, np.dtype(np.float32): capi.RAW_F32,
+               np.dtype(np.float64): capi.RAW_F64}
+
 _hip = None
 
 
@@ -51,6 +63,10 @@ def hip():
                                               ctypes.c_double, vp]
         L.afx_batch_export_statistics_device.argtypes = [vp, ctypes.POINTER(_DeviceOut), ctypes.c_int32, vp]
         L.afx_batch_export_frame_counts_device.argtypes = [vp, vp, vp]
+        L.afx_batch_create_from_raw_device.argtypes = [vp, ctypes.POINTER(_RawDevice), ctypes.c_int32, ctypes.c_uint32, vp, ctypes.POINTER(vp),
+                                                       ctypes.POINTER(capi._LoadInfo)]
+        L.afx_batch_export_samples_device.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, vp]
+        L.afx_batch_export_sample_counts_device.argtypes = [vp, vp, vp]
         _hip = L
     return _hip
 
@@ -217,6 +233,98 @@ def create_batch_from_device(plan, arrays, mask=capi.D_ALL_LOW_LEVEL, lengths=No
     b.plan, b.L, b.mask, b.n_bufs, b.h = plan, H, mask, n, h
     b.total_frames = int(H.afx_batch_total_frames(h))
     return b
+
+
+def _raw_device_spec(a, fmt, rate):
+    """an object with __cuda_array_interface__ -> (pointer, RAW_* code, channels, sample_rate, layout, n_frames, channel_stride)"""
+    if not hasattr(a, "__cuda_array_interface__"):
+        raise TypeError("a source exposes __cuda_array_interface__ (or is a tuple as afx_raw_device's fields)")
+    cai = a.__cuda_array_interface__
+    dt = np.dtype(cai["typestr"])
+    shape, strides, ptr = [int(s) for s in cai["shape"]], cai.get("strides"), cai["data"][0]
+    if strides is None:
+        strides = [int(np.prod(shape[i + 1:], dtype=np.int64)) * dt.itemsize for i in range(len(shape))]
+    strides = [int(s) for s in strides]
+    if fmt is None:
+        if dt not in _RAW_FORMAT:
+            raise TypeError("raw PCM is int16, int32, float32 or float64, or its format is given")
+        fmt = _RAW_FORMAT[dt]
+    fmt = int(fmt)
+    bps = capi._RAW_BYTES.get(fmt)
+    if bps is None:
+        raise ValueError("a format of 2, 3, 4 or 8 bytes a sample (a FLAC stream is indexed on the host: Plan.batch_from_raw)")
+    if dt.itemsize != bps:
+        # the array's bytes as they are (packed int24 in a uint8 array): one sample per run of bps bytes
+        if dt.itemsize != 1:
+            raise ValueError("an array of another element size than its format's holds bytes (uint8)")
+        if len(shape) == 1 and (strides[0] == 1 or shape[0] <= 1):
+            return ptr or None, fmt, 1, rate, RAW_INTERLEAVED, shape[0] // bps, 0
+        if len(shape) < 2 or shape[-1] != bps or strides[-1] != 1:
+            raise ValueError("bytes are 1-D (mono) or end in an axis of one sample's bytes")
+        shape, strides = shape[:-1], strides[:-1]
+    if len(shape) == 1:
+        if shape[0] > 1 and strides[0] != bps:
+            raise ValueError("a 1-D source is contiguous")
+        return ptr or None, fmt, 1, rate, RAW_INTERLEAVED, shape[0], 0
+    if len(shape) != 2:
+        raise ValueError("a source is 1-D (mono) or 2-D")
+    for c in (1, 0):   # [frames, channels] first: what a [2, 2] array is taken for
+        f = 1 - c
+        if shape[c] <= 8 and strides[c] == bps and strides[f] == shape[c] * bps:
+            return ptr or None, fmt, shape[c], rate, RAW_INTERLEAVED, shape[f], 0
+    for c in (0, 1):
+        f = 1 - c
+        if shape[c] <= 8 and strides[f] == bps and strides[c] >= 0 and strides[c] % bps == 0:
+            return ptr or None, fmt, shape[c], rate, RAW_PLANAR, shape[f], strides[c] // bps
+    raise ValueError("a 2-D source is interleaved (unit stride along at most 8 channels, frames channels apart) or planar (unit stride along the frames)")
+
+
+def create_batch_from_raw_device(plan, arrays, sample_rates=None, formats=None, mask=capi.D_ALL_LOW_LEVEL, stream=None):
+    """afx_batch_create_from_raw_device -> (capi.Batch, list of load-info dicts): the LoadSample front end on raw PCM in
+    device memory.  Each array is anything with __cuda_array_interface__ (or a tuple of afx_raw_device's fields as the C call
+    takes them: pointer, RAW_* code, channels, sample_rate, layout, n_frames, channel_stride).  1-D is mono.  2-D takes its
+    layout from the strides: unit stride along the channel axis and frames `channels` apart is interleaved; unit stride along
+    the frame axis is planar, the other stride being channel_stride; anything else raises ValueError.  Either axis order is
+    accepted: the axis of length <= 8 with the matching stride is the channel axis, and where both could be (a [2, 2] array)
+    the array is [frames, channels].  The format follows from the dtype (int16, int32, float32, float64); formats[i]
+    overrides it -- big-endian sources, and packed int24 in a uint8 array: 1-D (mono, n_frames = bytes // 3) or with a last
+    axis of 3 bytes.  sample_rates[i]: 0 or None is the plan's.  stream: the producer's.  Synchronous."""
+    H = hip()
+    n = len(arrays)
+    arr = (_RawDevice * max(1, n))()
+    for i, a in enumerate(arrays):
+        rate = int(sample_rates[i] or 0) if sample_rates is not None else 0
+        spec = tuple(a) if isinstance(a, (tuple, list)) else _raw_device_spec(a, formats[i] if formats is not None else None, rate)
+        arr[i].data, arr[i].format, arr[i].channels, arr[i].sample_rate, arr[i].layout, arr[i].n_frames, arr[i].channel_stride = spec
+    info = (capi._LoadInfo * max(1, n))()
+    h = ctypes.c_void_p()
+    capi._check(H, H.afx_batch_create_from_raw_device(plan.h, arr, n, mask, _stream_handle(stream), ctypes.byref(h), info))
+    b = capi.Batch.__new__(capi.Batch)
+    b.plan, b.L, b.mask, b.n_bufs, b.h = plan, H, mask, n, h
+    b.total_frames = int(H.afx_batch_total_frames(h))
+    infos = [{k: getattr(info[i], k) for k, _ in capi._LoadInfo._fields_ if k != "reserved"} for i in range(n)]
+    return b, infos
+
+
+def sample_counts(batch, stream=None):
+    """afx_batch_export_sample_counts_device -> DeviceArray int64 [n_bufs]: the analysed samples of every file"""
+    H = hip()
+    a = DeviceArray((batch.n_bufs,), np.int64)
+    capi._check(H, H.afx_batch_export_sample_counts_device(batch.h, a.ptr, _stream_handle(stream)))
+    return a
+
+
+def export_samples(batch, dtype=np.float32, pad=0.0, stream=None, max_samples=None):
+    """afx_batch_export_samples_device -> DeviceArray [n_bufs, max_samples]: the samples the kernels analyse (what
+    Batch.fetch_samples returns), `pad` behind every file's own.  max_samples: the longest file's unless given."""
+    H = hip()
+    code = _dtype_code(dtype)
+    if max_samples is None:
+        counts = sample_counts(batch).download()
+        max_samples = int(counts.max()) if counts.size else 0
+    a = DeviceArray((batch.n_bufs, max_samples), dtype)
+    capi._check(H, H.afx_batch_export_samples_device(batch.h, a.ptr or 1, code, max_samples, pad, _stream_handle(stream)))
+    return a
 
 
 def frame_offsets(batch):

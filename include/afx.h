@@ -430,6 +430,47 @@ int afx_batch_create_from_raw(afx_plan* plan, const afx_raw* raws, int32_t n_buf
 /* the normalised samples of buffer `buf` (its analysed prefix) for the CPU-resident neighbours */
 int afx_batch_fetch_samples(afx_batch* batch, int32_t buf, double* dst, int64_t n);
 
+/* ---- LoadSample on device-resident audio ----
+ * afx_batch_create_from_raw with the bytes in HBM: what a GPU decoder leaves (interleaved int16 / int24 at the file's own
+ * rate) or an augmentation pipeline ([channels, samples] float planes).  One gather launch moves the accepted buffers
+ * into the raw arena, a planar buffer interleaved on its way; every later step is afx_batch_create_from_raw's, and info,
+ * afx_batch_fetch_samples and every later fetch are bit-identical to that call on the same samples, interleaved.
+ * Synchronous like it: an event on producer_stream (NULL: the null stream) is waited for by the batch's stream, and the
+ * source may be freed or reused on return.
+ * Statuses are afx_batch_create_from_raw's, decided by the same code (the 16 x rate bound and the 2^30 converted samples
+ * included).  In addition, per buffer and before anything is enqueued: AFX_RAW_FLAC gets AFX_ERR_UNSUPPORTED (its index
+ * is read on the host); AFX_ERR_BAD_BUFFER goes to a layout that is neither of the two, a planar channel_stride below
+ * n_frames, a byte count or plane extent that overflows, and a range -- [data, data + n_frames x channels x bps)
+ * interleaved, [data, data + ((channels - 1) x channel_stride + n_frames) x bps) planar -- that does not lie inside ONE
+ * allocation on the plan's device.  `data` need only be aligned to its sample (packed int24: any byte).  A batch beyond
+ * the gather's 32-bit tile prefix is refused whole, AFX_ERR_INVALID_ARG. */
+enum { AFX_RAW_INTERLEAVED = 0, AFX_RAW_PLANAR = 1 };
+typedef struct {
+  const void* data;       /* DEVICE pointer on the plan's device */
+  int32_t format;         /* AFX_RAW_I16 .. AFX_RAW_F64_BE */
+  int32_t channels;       /* 1..8 */
+  int32_t sample_rate;    /* 0 = the plan's rate */
+  int32_t layout;         /* AFX_RAW_INTERLEAVED: frame-major as afx_raw.data; AFX_RAW_PLANAR: one plane per channel */
+  int64_t n_frames;       /* sample frames per channel */
+  int64_t channel_stride; /* planar: SAMPLES between the starts of consecutive planes, >= n_frames; interleaved: ignored */
+} afx_raw_device;
+int afx_batch_create_from_raw_device(afx_plan* plan, const afx_raw_device* raws, int32_t n_bufs, uint32_t mask,
+                                     void* producer_stream /* hipStream_t */, afx_batch** out_batch,
+                                     afx_load_info* info /* [n_bufs], optional */);
+
+/* The samples every kernel analyses (TSampleData::mData's analysed prefix, what afx_batch_fetch_samples returns) into
+ * device memory of the caller's: one row per file at dst + i x buf_stride elements, used[i] samples and behind them
+ * pad_value up to buf_stride.  AFX_PCM_F64: the double (double)x * FinalScaling as the kernels form it (an AFX_PCM_F64
+ * batch: its doubles; an AFX_PCM_F32 afx_batch_create batch: (double)x); AFX_PCM_F32: (float) of that double, round to
+ * nearest even.  Any batch, before or after a run.  One launch on the batch's stream; consumer_stream as for
+ * afx_batch_export_device.  AFX_ERR_INVALID_ARG, with nothing enqueued: buf_stride below the longest used[i], a dtype that
+ * is neither of the two, a NULL dst, an extent of n_bufs x buf_stride elements that overflows or does not lie inside ONE
+ * device allocation on the plan's device. */
+int afx_batch_export_samples_device(afx_batch* batch, void* dst, int32_t dtype /* AFX_PCM_F32 | AFX_PCM_F64 */,
+                                    int64_t buf_stride, double pad_value, void* consumer_stream);
+/* used[i]: the lengths that go with afx_batch_export_samples_device */
+int afx_batch_export_sample_counts_device(afx_batch* batch, int64_t* d_counts /* [n_bufs], device */, void* consumer_stream);
+
 /* ---- rhythm tracker (AFX_D_RHYTHM): SampleAnalyser.cpp:983-1048 ---- *
  * Per file: the two onset series of TRhythmTracker::Onsets (one value per 512/128 frame of the analysed prefix: the
  * median-removed onset function where an onset was detected, 0 elsewhere), and 14 scalars.  Everything runs on the GPU.
