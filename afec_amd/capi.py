@@ -88,7 +88,7 @@ EXPORTS = [
     "afx_extract_batch", "afx_batch_create", "afx_batch_total_frames", "afx_batch_run",
     "afx_batch_sync", "afx_batch_run_timed", "afx_batch_fetch", "afx_batch_fetch_statistics", "afx_batch_destroy",
     "afx_algorithmic_bytes_per_frame", "afx_batch_create_from_raw", "afx_batch_fetch_samples",
-    "afx_host_alloc", "afx_host_free", "afx_batch_record_layout", "afx_batch_fetch_records",
+    "afx_host_alloc", "afx_host_free", "afx_batch_record_layout", "afx_batch_fetch_records", "afx_batch_store_records",
     "afx_batch_set_file_info", "afx_batch_rhythm_frames", "afx_batch_fetch_rhythm", "afx_batch_fetch_onset_functions",
     "afx_plan_set_blocking_wait", "afx_batch_get_info", "afx_plan_probe_device", "afx_device_count",
     "afx_batch_fetch_high_level",
@@ -107,6 +107,13 @@ RAW_I16_BE, RAW_I24_BE, RAW_F32_BE, RAW_I32_BE, RAW_F64_BE = 5, 6, 7, 8, 9   # t
 RAW_FLAC = 10   # a FLAC stream, decoded on the GPU: afx_raw.data points at an afx_flac_stream (Plan.batch_from_raw takes the image)
 _RAW_BYTES = {RAW_I16: 2, RAW_I24: 3, RAW_F32: 4, RAW_I32: 4, RAW_F64: 8,
               RAW_I16_BE: 2, RAW_I24_BE: 3, RAW_F32_BE: 4, RAW_I32_BE: 4, RAW_F64_BE: 8}
+
+# the series of a record in afx_batch_record_layout's order (AFX_NUM_SERIES)
+RECORD_SERIES = ["mfcc", "spectral_rms", "spectral_centroid", "spectral_spread", "spectral_skewness", "spectral_kurtosis",
+                 "spectral_rolloff", "spectral_flatness", "spectral_flux", "spectrum_bands", "amplitude_peak", "amplitude_rms",
+                 "sub_rms", "sub_flatness", "sub_flux", "sub_complexity", "sub_contrast", "spectral_contrast", "amplitude_silence",
+                 "amplitude_envelope", "spectral_complexity", "auto_correlation", "f0", "f0_confidence", "failsafe_f0",
+                 "spectral_inharmonicity", "tristimulus1", "tristimulus2", "tristimulus3"]
 
 # afx_out fields: name -> width per frame, in declaration order
 OUT_FIELDS = [
@@ -320,6 +327,9 @@ def load_library():
     L.afx_host_alloc.argtypes = [i64]
     L.afx_host_free.argtypes = [vp]
     L.afx_host_free.restype = None
+    L.afx_batch_record_layout.argtypes = [vp, ctypes.POINTER(i32), vp, vp]
+    L.afx_batch_fetch_records.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.afx_batch_store_records.argtypes = [vp, vp, vp, vp]
     L.afx_batch_set_file_info.argtypes = [vp, vp]
     L.afx_batch_rhythm_frames.restype = i64
     L.afx_batch_rhythm_frames.argtypes = [vp, vp]
@@ -839,6 +849,56 @@ class Batch:
         _check(self.L, self.L.afx_batch_fetch_statistics(self.h, ctypes.byref(out)))
         res["stats_status"] = st[:self.n_bufs]
         return res
+
+    def record_layout(self):
+        """afx_batch_record_layout -> dict: "stride" (doubles per record), "offsets" {series: first column, -1 when the
+        series is not in the mask} and "widths" {series: columns}, RECORD_SERIES order"""
+        stride = ctypes.c_int32()
+        offsets, widths = np.zeros(len(RECORD_SERIES), dtype=np.int32), np.zeros(len(RECORD_SERIES), dtype=np.int32)
+        _check(self.L, self.L.afx_batch_record_layout(self.h, ctypes.byref(stride), offsets.ctypes.data, widths.ctypes.data))
+        return {"stride": stride.value, "offsets": dict(zip(RECORD_SERIES, offsets.tolist())),
+                "widths": dict(zip(RECORD_SERIES, widths.tolist()))}
+
+    def fetch_records(self, statistics=None):
+        """afx_batch_fetch_records: the raw records as the kernels leave them -> dict: "records" [F][stride],
+        "frame_offset" [n_bufs + 1], "buf_status" [n_bufs], with AFX_D_STATISTICS in the mask (statistics=False leaves them
+        out) "statistics" [n_bufs][stride][13], with AFX_D_EFFECTIVE_LENGTH "effective_length" [n_bufs][3]"""
+        n, stride = self.n_bufs, self.record_layout()["stride"]
+        if statistics is None:
+            statistics = bool(self.mask & D_STATISTICS)
+        res = {"records": np.zeros((self.total_frames, stride)), "frame_offset": np.zeros(n + 1, dtype=np.int64),
+               "buf_status": np.zeros(max(1, n), dtype=np.int32)}
+        if statistics:
+            res["statistics"] = np.zeros((n, stride, NUM_STATISTICS))
+        if self.mask & D_EFFECTIVE_LENGTH:
+            res["effective_length"] = np.zeros((max(1, n), 3))
+
+        def ptr(k):
+            return res[k].ctypes.data if k in res and res[k].size else None
+        _check(self.L, self.L.afx_batch_fetch_records(self.h, ptr("records"), ptr("statistics"), ptr("frame_offset"), ptr("buf_status"),
+                                                      ptr("effective_length")))
+        res["buf_status"] = res["buf_status"][:n]
+        if "effective_length" in res:
+            res["effective_length"] = res["effective_length"][:n]
+        return res
+
+    def store_records(self, records=None, statistics=None, rhythm_scalars=None):
+        """afx_batch_store_records: overwrite what the last run left in device memory -- records [F][stride], statistics
+        [n_bufs][stride][13], rhythm_scalars [n_bufs][14] (RHYTHM_SCALARS order), float64 and C-contiguous, each optional --
+        so that every later fetch of the batch reads these values; the next run() overwrites them."""
+        stride = self.record_layout()["stride"]
+        shapes = {"records": (self.total_frames, stride), "statistics": (self.n_bufs, stride, NUM_STATISTICS),
+                  "rhythm_scalars": (self.n_bufs, len(RHYTHM_SCALARS))}
+        given = {"records": records, "statistics": statistics, "rhythm_scalars": rhythm_scalars}
+        ptrs = []
+        for name, a in given.items():
+            if a is None:
+                ptrs.append(None)
+                continue
+            if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.shape != shapes[name] or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{name} must be a C-contiguous float64 array of shape {shapes[name]}")
+            ptrs.append(a.ctypes.data if a.size else None)
+        _check(self.L, self.L.afx_batch_store_records(self.h, *ptrs))
 
     def set_file_info(self, info):
         """info: per buffer (original_sample_rate, data_offset, original_samples) -- what TSampleData carries besides

@@ -178,6 +178,25 @@ int afx_batch_fetch_records(afx_batch* b, double* records, double* statistics, i
   return AFX_OK;
 }
 
+int afx_batch_store_records(afx_batch* b, const double* records, const double* statistics, const double* rhythm_scalars) {
+  if (!b) return fail(AFX_ERR_INVALID_ARG, "null batch");
+  if (!b->ran) return fail(AFX_ERR_INVALID_ARG, "afx_batch_store_records before afx_batch_run (the next run would overwrite what is stored)");
+  if (statistics && !b->want_stats) return fail(AFX_ERR_INVALID_ARG, "AFX_D_STATISTICS was not in the batch mask");
+  if (rhythm_scalars && !(b->mask & AFX_D_RHYTHM)) return fail(AFX_ERR_INVALID_ARG, "AFX_D_RHYTHM was not in the batch mask");
+  if (b->n_bufs == 0 || b->total_frames == 0 || (!records && !statistics && !rhythm_scalars)) return AFX_OK;
+  // the inverse of afx_batch_fetch_records' and afx_batch_fetch_rhythm's transfers, behind the run on the batch's stream
+  struct Upload { void* dst; const void* src; size_t bytes; };
+  const size_t stride = (size_t)b->lay.stride;
+  const Upload items[3] = {{b->d_rec, records, (size_t)b->total_frames * stride * sizeof(double)},
+                           {b->d_stats, statistics, (size_t)b->n_bufs * stride * AFX_NUM_STATISTICS * sizeof(double)},
+                           {b->d_rt_scalars, rhythm_scalars, (size_t)b->n_bufs * AFX_NUM_RHYTHM_SCALARS * sizeof(double)}};
+  HIP_TRY(hipSetDevice(b->plan->desc.device));
+  for (const Upload& u : items)
+    if (u.src && u.bytes) HIP_TRY(hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));   // the caller's arrays are pageable host memory that may change again
+  return AFX_OK;
+}
+
 int afx_batch_set_file_info(afx_batch* b, const afx_file_info* info) {
   if (!b || !info) return fail(AFX_ERR_INVALID_ARG, "null argument");
   if (!(b->mask & AFX_D_RHYTHM)) return fail(AFX_ERR_INVALID_ARG, "AFX_D_RHYTHM was not in the batch mask");

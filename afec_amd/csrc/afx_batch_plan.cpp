@@ -473,6 +473,7 @@ int build_batch(afx_plan* plan, const BatchSource& src, afx_batch** out_batch) {
   b->plan = plan;
   plan->refs.fetch_add(1);
   b->mask = p.mask;
+  b->want_stats = p.want_stats;
   b->n_bufs = src.n_bufs;
   b->lay = make_layout(p.mask);
   // flux, the sub-band descriptors and the whitened-spectrum neighbours are computed from the stored

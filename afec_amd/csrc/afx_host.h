@@ -193,7 +193,8 @@ struct afx_plan {
 
 struct afx_batch {
   afx_plan* plan = nullptr;
-  uint32_t mask = 0;
+  uint32_t mask = 0;               // the descriptor bits; AFX_D_STATISTICS is taken out and kept in want_stats
+  bool want_stats = false;
   int pcm_dtype = afx::kPcmF32;   // afx::kPcm*: the ABI's AFX_PCM_F32 / AFX_PCM_F64, or kPcmScaledF32 behind the LoadSample front end
   int32_t n_bufs = 0;
   std::vector<int64_t> frame_offset;  // [n_bufs+1]

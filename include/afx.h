@@ -294,6 +294,19 @@ int afx_batch_record_layout(const afx_batch* batch, int32_t* stride, int32_t* of
                             int32_t* widths /* [AFX_NUM_SERIES] */);
 int afx_batch_fetch_records(afx_batch* batch, double* records, double* statistics, int64_t* frame_offset /* [n_bufs+1] */,
                             int32_t* buf_status /* [n_bufs] */, double* effective_length /* [n_bufs][3] or NULL */);
+/* The inverse: overwrites, in device memory, what the last afx_batch_run left -- the records (afx_batch_record_layout's
+ * layout), the statistics, and the rhythm tracker's scalars as afx_batch_fetch_rhythm hands them out -- with the caller's.
+ * For a pipeline that kept the records of an earlier run and wants the fetches above a run (high level, classification
+ * features, class signature and decision, text, row) from them without analysing the audio again, and for tests that feed
+ * those kernels chosen values.  Frame offsets, buffer status and effective lengths stay the batch's; every later fetch of
+ * the batch, device exports included, reads the stored values; the next afx_batch_run overwrites them.  Nothing is
+ * computed: three host-to-device copies on the batch's stream, waited for (the caller's memory may be pageable).  Any
+ * pointer may be NULL (that part stays as it is); all three NULL, n_bufs == 0 or no frames at all: AFX_OK, nothing moves.
+ * AFX_ERR_INVALID_ARG: a null batch, a call before the first afx_batch_run, statistics without AFX_D_STATISTICS in the
+ * mask, rhythm_scalars without AFX_D_RHYTHM -- by the mask alone, a batch without buffers included.  Additive (ABI 7). */
+int afx_batch_store_records(afx_batch* batch, const double* records /* [total_frames][stride] or NULL */,
+                            const double* statistics /* [n_bufs][stride][AFX_NUM_STATISTICS] or NULL */,
+                            const double* rhythm_scalars /* [n_bufs][AFX_NUM_RHYTHM_SCALARS] or NULL */);
 
 /* ---- device-resident input and output ----
  * For a consumer or producer on the same GPU that the library does not own (a model, an index, a decoder that has left

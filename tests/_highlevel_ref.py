@@ -88,10 +88,12 @@ def class_margin(series):
     return min(abs(m - CLASS_THRESHOLDS[0]), abs(m - CLASS_THRESHOLDS[1]))
 
 
-def high_level(series, final_tempo, final_tempo_confidence, peak_value=None, rms_value=None, sample_rate=44100):
+def high_level(series, final_tempo, final_tempo_confidence, peak_value=None, rms_value=None, sample_rate=44100, trace=None):
     """series: dict of the SERIES arrays of one file ([F] each, spectrum_bands [F][28]).
     -> dict: "scalars" [15] (SCALARS order), "signature" [64][14], "pitch" [F], "peak" [F].
-    A file without frames yields zeros (the reference's resampling loop is undefined for it)."""
+    A file without frames yields zeros (the reference's resampling loop is undefined for it).
+    trace: a dict that is filled with the intermediate values of the flow (what decided what) -- for tests that must
+    know which branch a chosen input took (tests/test_records_cases_cpu.py); the result does not depend on it."""
     g = {k: np.asarray(series[k], dtype=np.float64) for k in SERIES}
     frames = g["f0"].size
     if frames == 0:
@@ -111,6 +113,7 @@ def high_level(series, final_tempo, final_tempo_confidence, peak_value=None, rms
     confident = np.array([is_confident(f0[i], conf[i]) for i in range(frames)], dtype=bool)
     pitches = f0[confident]
     base_note = -1.0
+    hz = deviation = math.nan
     if pitches.size:
         hz = _oracle.stat("median", pitches)
         if hz > 20 and hz < quarter:
@@ -133,15 +136,19 @@ def high_level(series, final_tempo, final_tempo_confidence, peak_value=None, rms
     rolloff, centroid, flatness = g["spectral_rolloff"][audible], g["spectral_centroid"][audible], g["spectral_flatness"][audible]
     acorr = g["auto_correlation"][audible]
     brightness = noisiness = harmonicity = 0.0
+    weights = {}
     if rolloff.size:
         w = freq_to_midi(_mean(rolloff)) / 128.0 * 0.7 + freq_to_midi(_oracle.stat("max", centroid)) / 128.0 * 0.3
+        weights["brightness"] = w
         w = _mmax(0.0, _mmin(1.0, w))
         brightness = math.pow(w, 4.0)
         w = ((1.0 - _oracle.stat("min", flatness)) * 0.2 + (1.0 - _mean(flatness)) * 0.6 +
              (1.0 - _oracle.stat("max", flatness)) * 0.2)
+        weights["noisiness"] = w
         w = _mmax(0.0, _mmin(1.0, w))
         noisiness = math.pow(w, 2.0)
         w = _mmin(1.0, 1.5 * _mean(acorr)) * 0.4 + _mmin(1.0, 2.0 * conf_mean) * 0.3 + _mean(flatness) * 0.3
+        weights["harmonicity"] = w
         w = _mmax(0.0, _mmin(1.0, w))
         harmonicity = math.pow(w, 2.0)
 
@@ -173,16 +180,27 @@ def high_level(series, final_tempo, final_tempo_confidence, peak_value=None, rms
 
     # ... Pitch (:1557-1596)
     last_pitch = 0.0
+    look_ahead_hit = -1
     if frames > 1:
         for i in range(max(1, frames // 4) + 1):
             if audible[i] and confident[i]:
                 last_pitch = f0[i]
+                look_ahead_hit = i
                 break
     pitch = np.zeros(frames)
+    pitch_hz = np.zeros(frames)
     for i in range(frames):
         if audible[i] and confident[i]:
             last_pitch = f0[i]
+        pitch_hz[i] = last_pitch
         pitch[i] = freq_to_midi(last_pitch)
+
+    if trace is not None:
+        trace.update(frames=frames, audible=audible, conf_mean=conf_mean, threshold=threshold, confident=confident,
+                     pitches=pitches, median_hz=hz, deviation=deviation if base_note > 0.0 else math.nan, weights=weights,
+                     auto_correlation_mean=_mean(acorr), look_ahead_last=max(1, frames // 4) if frames > 1 else -1,
+                     look_ahead_hit=look_ahead_hit, pitch_hz=pitch_hz, final_tempo=float(final_tempo),
+                     rolloff_mean=_mean(rolloff), centroid_max=_oracle.stat("max", centroid) if centroid.size else math.nan)
 
     scalars = np.array([peak_db, rms_db, base_note, base_note_confidence, bpm, float(final_tempo_confidence), brightness,
                         noisiness, harmonicity] + means + [conf_mean])

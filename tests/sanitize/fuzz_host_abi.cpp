@@ -9,6 +9,8 @@
 //   * afx_batch_create_from_raw: every sample type, 1 .. 8 channels, silence at either end, all-silent files, files at other
 //     rates (converted; refused: above 16 x the rate, >= 2^30 converted samples), contiguous staging and scattered
 //     buffers, >= 768 files (whole-file whitening chunks), the rhythm tracker's long-file path, afx_batch_set_file_info;
+//     afx_batch_store_records of random bytes over the run's records, statistics and rhythm scalars, fetched back and
+//     compared byte for byte, with its refusals (before the run, a part the mask lacks, a null batch);
 //   * the fetches above a run (afx_block.h lays out their blocks): batches of 0, 1, 2, 3 and 5 buffers -- none, one, three
 //     and 65 frames, a refused one -- through afx_batch_fetch_high_level, _classification_features, _class_signature and
 //     _class_decision in random order on the one reused result block, with and without levels, with a class model, a
@@ -39,7 +41,7 @@
 
 namespace {
 
-std::atomic<long> g_batches{0}, g_frames{0}, g_refused{0}, g_oom{0}, g_fetch_batches{0}, g_fetches{0}, g_fetch_oom{0};
+std::atomic<long> g_batches{0}, g_frames{0}, g_refused{0}, g_oom{0}, g_fetch_batches{0}, g_fetches{0}, g_fetch_oom{0}, g_stores{0};
 
 [[noreturn]] void die(const char* what, long long a = 0, long long b = 0) {
   std::fprintf(stderr, "fuzz_host_abi: FAILED: %s (%lld, %lld); last error: %s\n", what, a, b, afx_last_error());
@@ -195,6 +197,14 @@ void round_create(afx_plan* plan, int64_t cap_samples, Rng& r, bool inject) {
       REQUIRE(afx_batch_fetch_onset_functions(b, odf.data()) == AFX_OK);
     }
   }
+  {
+    // afx_batch_store_records refuses by the mask, whatever the batch holds (an empty one included); what it accepts on a
+    // batch without buffers or frames moves nothing
+    const double one = 0.0;
+    if (!(mask & AFX_D_STATISTICS)) REQUIRE(afx_batch_store_records(b, nullptr, &one, nullptr) == AFX_ERR_INVALID_ARG && std::strcmp(afx_last_error(), "AFX_D_STATISTICS was not in the batch mask") == 0);
+    if (!(mask & AFX_D_RHYTHM)) REQUIRE(afx_batch_store_records(b, nullptr, nullptr, &one) == AFX_ERR_INVALID_ARG && std::strcmp(afx_last_error(), "AFX_D_RHYTHM was not in the batch mask") == 0);
+    if (total == 0) REQUIRE(afx_batch_store_records(b, &one, (mask & AFX_D_STATISTICS) ? &one : nullptr, (mask & AFX_D_RHYTHM) ? &one : nullptr) == AFX_OK);
+  }
   g_frames += total;
   ++g_batches;
   afx_batch_destroy(b);
@@ -266,6 +276,13 @@ void round_raw(afx_plan* plan, Rng& r, bool inject) {
     ++g_oom;
     return;
   }
+  {
+    // afx_batch_store_records has nothing to overwrite before the first run, and no batch to do it in without one
+    const double one = 0.0;
+    REQUIRE(afx_batch_store_records(b, &one, nullptr, nullptr) == AFX_ERR_INVALID_ARG);
+    REQUIRE(std::strstr(afx_last_error(), "afx_batch_store_records before afx_batch_run") == afx_last_error());
+    REQUIRE(afx_batch_store_records(nullptr, &one, nullptr, nullptr) == AFX_ERR_INVALID_ARG && std::strcmp(afx_last_error(), "null batch") == 0);
+  }
   REQUIRE(afx_batch_run(b) == AFX_OK);
   int32_t stride = 0, offsets[AFX_NUM_SERIES], widths[AFX_NUM_SERIES];
   REQUIRE(afx_batch_record_layout(b, &stride, offsets, widths) == AFX_OK);
@@ -285,6 +302,45 @@ void round_raw(afx_plan* plan, Rng& r, bool inject) {
     const int64_t rows = afx_batch_rhythm_frames(b, roff.data());
     std::vector<double> onsets((size_t)rows * 2), scalars((size_t)n * 14), ostats((size_t)n * 26);
     REQUIRE(afx_batch_fetch_rhythm(b, onsets.data(), scalars.data(), (mask & AFX_D_STATISTICS) ? ostats.data() : nullptr) == AFX_OK);
+  }
+  {
+    // afx_batch_store_records: what is stored comes back byte for byte (NaNs with a payload among it), a NULL part stays
+    // as it was, the parts the mask lacks are refused, and offsets and status are the batch's own
+    const bool with_stats = (mask & AFX_D_STATISTICS) != 0, with_rhythm = (mask & AFX_D_RHYTHM) != 0;
+    auto scribble = [&r](std::vector<double>& v) {
+      for (double& x : v) {
+        const uint64_t bits = r.chance(10) ? 0x7FF8000000000000ull | (r.g() & 0xFFFFFull) : r.g();
+        std::memcpy(&x, &bits, 8);
+      }
+    };
+    std::vector<double> rec2(rec.size()), stats2(stats.size()), rhythm2(with_rhythm ? (size_t)n * AFX_NUM_RHYTHM_SCALARS : 0);
+    scribble(rec2); scribble(stats2); scribble(rhythm2);
+    const double one = 0.0;
+    if (!with_stats) {
+      REQUIRE(afx_batch_store_records(b, nullptr, &one, nullptr) == AFX_ERR_INVALID_ARG && std::strcmp(afx_last_error(), "AFX_D_STATISTICS was not in the batch mask") == 0);
+    }
+    if (!with_rhythm) {
+      REQUIRE(afx_batch_store_records(b, nullptr, nullptr, &one) == AFX_ERR_INVALID_ARG && std::strcmp(afx_last_error(), "AFX_D_RHYTHM was not in the batch mask") == 0);
+    }
+    REQUIRE(afx_batch_store_records(b, nullptr, nullptr, nullptr) == AFX_OK);
+    const bool skip_records = r.chance(20);
+    REQUIRE(afx_batch_store_records(b, skip_records || rec2.empty() ? nullptr : rec2.data(), with_stats ? stats2.data() : nullptr,
+                                    with_rhythm ? rhythm2.data() : nullptr) == AFX_OK);
+    std::vector<double> rec3(rec.size()), stats3(stats.size()), rhythm3(rhythm2.size());
+    std::vector<int64_t> off3((size_t)n + 1);
+    std::vector<int32_t> status3((size_t)n);
+    REQUIRE(afx_batch_fetch_records(b, rec3.empty() ? nullptr : rec3.data(), stats3.empty() ? nullptr : stats3.data(), off3.data(), status3.data(), nullptr) == AFX_OK);
+    const std::vector<double>& rec_want = skip_records ? rec : rec2;
+    REQUIRE(rec3.empty() || std::memcmp(rec3.data(), rec_want.data(), rec3.size() * sizeof(double)) == 0);
+    // (a batch without frames moves nothing: its statistics stay the run's)
+    const std::vector<double>& stats_want = total > 0 ? stats2 : stats;
+    REQUIRE(stats3.empty() || std::memcmp(stats3.data(), stats_want.data(), stats3.size() * sizeof(double)) == 0);
+    REQUIRE(off3 == off && status3 == status);
+    if (with_rhythm && total > 0) {
+      REQUIRE(afx_batch_fetch_rhythm(b, nullptr, rhythm3.data(), nullptr) == AFX_OK);
+      REQUIRE(std::memcmp(rhythm3.data(), rhythm2.data(), rhythm3.size() * sizeof(double)) == 0);
+    }
+    ++g_stores;
   }
   {
     const int pick = (int)r.range(0, n - 1);
@@ -757,8 +813,8 @@ int main(int argc, char** argv) {
   REQUIRE(hipstub::device_bytes_in_use() == 0, (long long)hipstub::device_bytes_in_use());
   REQUIRE(hipstub::live_streams() == 0 && hipstub::live_events() == 0, hipstub::live_streams(), hipstub::live_events());
   std::printf("fuzz_host_abi: %ld batches, %ld frames, %ld refused files, %ld injected allocation failures survived; %ld batches through %ld fetches above a run, "
-              "%ld allocation failures inside a fetch survived; %d thread(s), seed %llu: clean\n",
-              g_batches.load(), g_frames.load(), g_refused.load(), g_oom.load(), g_fetch_batches.load(), g_fetches.load(), g_fetch_oom.load(), threads,
+              "%ld allocation failures inside a fetch survived; %ld stored records read back; %d thread(s), seed %llu: clean\n",
+              g_batches.load(), g_frames.load(), g_refused.load(), g_oom.load(), g_fetch_batches.load(), g_fetches.load(), g_fetch_oom.load(), g_stores.load(), threads,
               (unsigned long long)seed);
   return 0;
 }

@@ -28,6 +28,17 @@ def test_header_and_binding_agree():
     assert header_functions() == sorted(capi.EXPORTS)
 
 
+def test_binding_names_the_record_series_in_the_header_s_order():
+    """capi.RECORD_SERIES is afx_batch_record_layout's series order as include/afx.h states it, AFX_NUM_SERIES of them, and
+    the same series afx_out carries (all of its fields but the magnitudes, which lie outside the records)"""
+    text = open(os.path.join(ROOT, "include", "afx.h")).read()
+    listed = re.search(r"Series order \(= record order\):(.*?)\.\s*\n\s*\* Either destination", text, flags=re.S).group(1)
+    names = [n.strip() for n in re.sub(r"[*\n]", " ", listed).split(",")]
+    assert names == capi.RECORD_SERIES
+    assert len(capi.RECORD_SERIES) == int(re.search(r"#define AFX_NUM_SERIES (\d+)", text).group(1))
+    assert sorted(capi.RECORD_SERIES) == sorted(n for n, _ in capi.OUT_FIELDS if n != "magnitude")
+
+
 def test_library_exports_every_declared_symbol(lib):
     for name in header_functions():
         assert hasattr(lib, name), name
