@@ -21,4 +21,5 @@ from .device import (  # noqa: F401
     DeviceArray, Stream, create_batch_from_device, export, export_into, export_statistics, features, frame_counts,
     EXPORT_PACKED, EXPORT_PADDED, SERIES, SERIES_MAGNITUDE,
     create_batch_from_raw_device, export_samples, sample_counts, RAW_INTERLEAVED, RAW_PLANAR,
+    file_results, file_results_into, embedding, FILE_KINDS,
 )

@@ -101,6 +101,7 @@ EXPORTS = [
     "afx_batch_create_from_device", "afx_batch_export_device", "afx_batch_export_statistics_device",
     "afx_batch_export_frame_counts_device",
     "afx_batch_create_from_raw_device", "afx_batch_export_samples_device", "afx_batch_export_sample_counts_device",
+    "afx_batch_export_file_results_device",
 ]
 RAW_I16, RAW_I24, RAW_F32, RAW_I32, RAW_F64 = 0, 1, 2, 3, 4
 RAW_I16_BE, RAW_I24_BE, RAW_F32_BE, RAW_I32_BE, RAW_F64_BE = 5, 6, 7, 8, 9   # the same with Motorola byte order (AIFF)

@@ -40,9 +40,13 @@ const T* at(const char* base, size_t offset) { return reinterpret_cast<const T*>
 
 // The workspace's result buffer on the device and the page-locked one it lands in, reserved for one fetch's layout (the
 // fetches are synchronous: one at a time uses them).  n: the batch's buffers; 0: nothing reserved, nothing to launch.
+// `uploaded`: an event the enqueue halves below record on the batch's stream directly behind each copy out of `host`, for a
+// caller that returns without waiting for the stream (afx_device_file_io.cpp) and so has to know when `host` may be written
+// again; nullptr (every synchronous fetch): nothing is recorded.
 struct ResultBlock {
   size_t n = 0;
   char *dev = nullptr, *host = nullptr;
+  hipEvent_t uploaded = nullptr;
 };
 
 #define AFX_TRY(expr)                   \

@@ -88,6 +88,7 @@ int enqueue_features(afx_batch* b, const FeatureBlock& fb, const ResultBlock& rb
   fb.point(&a, rb.dev);
 
   HIP_TRY(hipMemcpyAsync(rb.dev + fb.efflen12, rb.host + fb.efflen12, fb.end - fb.efflen12, hipMemcpyHostToDevice, b->stream));
+  if (rb.uploaded) HIP_TRY(hipEventRecord(rb.uploaded, b->stream));
   HIP_TRY(afx::launch_classification_features(a, b->stream));
   return AFX_OK;
 }

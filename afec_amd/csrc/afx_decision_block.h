@@ -29,6 +29,23 @@ inline afx::GbdtArgs gbdt_args(const afx_model* model, char* base, size_t featur
   return g;
 }
 
+// What class_signature_kernel writes for one bagging: what a signature fetch brings back (afx_class_decision.cpp) and the
+// export of the per-file results leaves on the device (afx_device_file_io.cpp).
+struct SignatureBlock {
+  size_t n, n_classes, n_models, signature, iterations_used, non_finite, end;
+  SignatureBlock(Layout& l, size_t n_vectors, const afx::GbdtModel& m) : n(n_vectors), n_classes((size_t)m.n_classes), n_models((size_t)m.n_models) {
+    signature = l.take<float>(n * n_classes);
+    iterations_used = l.take<int32_t>(n * n_models);
+    non_finite = l.take<int32_t>(n);
+    end = l.bytes();
+  }
+  void hand_out(const char* host, float* out_signature, int32_t* out_iterations_used, int32_t* out_non_finite) const {
+    std::memcpy(out_signature, host + signature, n * n_classes * sizeof(float));
+    if (out_iterations_used) std::memcpy(out_iterations_used, host + iterations_used, n * n_models * sizeof(int32_t));
+    if (out_non_finite) std::memcpy(out_non_finite, host + non_finite, n * sizeof(int32_t));
+  }
+};
+
 // What afx_decision_out names: the two signatures (a model that is not there has an array of no length), which the decision
 // kernel reads, then what it writes.
 struct DecisionBlock {

@@ -22,28 +22,6 @@ using namespace afx::host;
 
 namespace {
 
-// what the runtime says of a pointer (nothing is enqueued, nothing is read through it)
-DevioAlloc ask_runtime(const void* p) {
-  DevioAlloc a;
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();   // a pointer the runtime does not know is an answer, not a failure of the call
-    return a;
-  }
-  if (attr.type != hipMemoryTypeDevice) return a;
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-    (void)hipGetLastError();
-    return a;
-  }
-  a.device = true;
-  a.ordinal = attr.device;
-  a.base = (uint64_t)(uintptr_t)base;
-  a.size = (uint64_t)size;
-  return a;
-}
-
 hipError_t devio_event(Workspace* ws) {
   return ws->ev_devio ? hipSuccess : hipEventCreateWithFlags(&ws->ev_devio, hipEventDisableTiming);
 }
@@ -94,7 +72,7 @@ struct BatchShape : ExportShape {
 bool destinations_ok(const afx_batch* b, const afx_device_out* outs, const std::vector<uint64_t>& extent_bytes) {
   std::vector<DevioAlloc> allocs(extent_bytes.size());
   for (size_t k = 0; k < extent_bytes.size(); ++k)
-    if (extent_bytes[k] > 0) allocs[k] = ask_runtime(outs[k].dst);
+    if (extent_bytes[k] > 0) allocs[k] = devio_ask_runtime(outs[k].dst);
   return devio_extents_ok(outs, extent_bytes, allocs.data(), b->plan->desc.device);
 }
 
@@ -146,8 +124,35 @@ int device_sample_rows(afx_batch* b) {
   return AFX_OK;
 }
 
+}  // namespace
+
+namespace afx {
+namespace host {
+
+// what the runtime says of a pointer (nothing is enqueued, nothing is read through it)
+DevioAlloc devio_ask_runtime(const void* p) {
+  DevioAlloc a;
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();   // a pointer the runtime does not know is an answer, not a failure of the call
+    return a;
+  }
+  if (attr.type != hipMemoryTypeDevice) return a;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+    (void)hipGetLastError();
+    return a;
+  }
+  a.device = true;
+  a.ordinal = attr.device;
+  a.base = (uint64_t)(uintptr_t)base;
+  a.size = (uint64_t)size;
+  return a;
+}
+
 // the consumer's stream behind the launch, or the host
-int hand_over(afx_batch* b, void* consumer_stream) {
+int devio_hand_over(afx_batch* b, void* consumer_stream) {
   if (!consumer_stream) {
     HIP_TRY(wait_for_stream(b->ws, b->stream));
     return AFX_OK;
@@ -158,7 +163,8 @@ int hand_over(afx_batch* b, void* consumer_stream) {
   return AFX_OK;
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace afx
 
 extern "C" {
 
@@ -170,7 +176,7 @@ int afx_batch_create_from_device(afx_plan* plan, const afx_buf* bufs, int32_t n_
   HIP_TRY(hipSetDevice(plan->desc.device));
   std::vector<DevioAlloc> allocs((size_t)n_bufs);
   for (int32_t i = 0; i < n_bufs; ++i)
-    if (devio_buffer_is_read(bufs[i])) allocs[(size_t)i] = ask_runtime(bufs[i].pcm);
+    if (devio_buffer_is_read(bufs[i])) allocs[(size_t)i] = devio_ask_runtime(bufs[i].pcm);
   const std::vector<afx_buf> checked = devio_checked_buffers(bufs, allocs.data(), n_bufs, plan->desc.device);
   DeviceBuffers ctx{checked.data(), n_bufs, (hipStream_t)producer_stream, {}};
   return batch_create_filled(plan, checked.data(), n_bufs, mask, first_valid_dtype(checked.data(), n_bufs), fill_from_device, &ctx,
@@ -194,7 +200,7 @@ int afx_batch_export_device(afx_batch* b, const afx_device_out* outs, int32_t n_
   p.args.mag = b->d_mag;
   p.args.frame_offset = b->d_devio_foff;
   HIP_TRY(afx::launch_devio_export(p.args, b->stream));
-  return hand_over(b, consumer_stream);
+  return devio_hand_over(b, consumer_stream);
 }
 
 int afx_batch_export_statistics_device(afx_batch* b, const afx_device_out* outs, int32_t n_outs, void* consumer_stream) {
@@ -207,7 +213,7 @@ int afx_batch_export_statistics_device(afx_batch* b, const afx_device_out* outs,
     return fail(AFX_ERR_INVALID_ARG, "a destination's extent does not lie inside one device allocation on the plan's device");
   p.args.stats = b->d_stats;
   HIP_TRY(afx::launch_devio_export_stats(p.args, b->stream));
-  return hand_over(b, consumer_stream);
+  return devio_hand_over(b, consumer_stream);
 }
 
 int afx_batch_export_frame_counts_device(afx_batch* b, int64_t* d_counts, void* consumer_stream) {
@@ -224,7 +230,7 @@ int afx_batch_export_frame_counts_device(afx_batch* b, int64_t* d_counts, void* 
     if (st != AFX_OK) return st;
     HIP_TRY(afx::launch_devio_frame_counts(b->d_devio_foff, b->n_bufs, d_counts, b->stream));
   }
-  return hand_over(b, consumer_stream);
+  return devio_hand_over(b, consumer_stream);
 }
 
 int afx_batch_create_from_raw_device(afx_plan* plan, const afx_raw_device* raws, int32_t n_bufs, uint32_t mask, void* producer_stream,
@@ -236,7 +242,7 @@ int afx_batch_create_from_raw_device(afx_plan* plan, const afx_raw_device* raws,
   HIP_TRY(hipSetDevice(plan->desc.device));
   std::vector<DevioAlloc> allocs((size_t)n_bufs);
   for (int32_t i = 0; i < n_bufs; ++i)
-    if (devio_raw_is_read(raws[i])) allocs[(size_t)i] = ask_runtime(raws[i].data);
+    if (devio_raw_is_read(raws[i])) allocs[(size_t)i] = devio_ask_runtime(raws[i].data);
   const std::vector<afx_raw> checked = devio_raw_checked(raws, allocs.data(), n_bufs, plan->desc.device);
   // afx_batch_create_from_raw's plan of the same buffers, made without the FLAC decoder: a stream's descriptor would be
   // read on the host
@@ -256,7 +262,7 @@ int afx_batch_export_samples_device(afx_batch* b, void* dst, int32_t dtype, int6
   if (p.status != AFX_OK) return fail(p.status, p.why);
   HIP_TRY(hipSetDevice(b->plan->desc.device));
   if (p.extent_bytes > 0) {
-    if (!devio_range_ok(ask_runtime(dst), b->plan->desc.device, dst, p.extent_bytes))
+    if (!devio_range_ok(devio_ask_runtime(dst), b->plan->desc.device, dst, p.extent_bytes))
       return fail(AFX_ERR_INVALID_ARG, "the destination's extent does not lie inside one device allocation on the plan's device");
     const int st = device_sample_rows(b);
     if (st != AFX_OK) return st;
@@ -265,7 +271,7 @@ int afx_batch_export_samples_device(afx_batch* b, void* dst, int32_t dtype, int6
     a.n_bufs = b->n_bufs; a.pcm_kind = b->pcm_dtype; a.f32 = p.f32; a.tiles_per_row = p.tiles_per_row;
     HIP_TRY(afx::launch_devio_samples(a, b->stream));
   }
-  return hand_over(b, consumer_stream);
+  return devio_hand_over(b, consumer_stream);
 }
 
 int afx_batch_export_sample_counts_device(afx_batch* b, int64_t* d_counts, void* consumer_stream) {
@@ -273,13 +279,13 @@ int afx_batch_export_sample_counts_device(afx_batch* b, int64_t* d_counts, void*
   if (b->n_bufs > 0 && !d_counts) return fail(AFX_ERR_INVALID_ARG, "null destination");
   HIP_TRY(hipSetDevice(b->plan->desc.device));
   if (b->n_bufs > 0) {
-    if (!devio_range_ok(ask_runtime(d_counts), b->plan->desc.device, d_counts, (uint64_t)b->n_bufs * sizeof(int64_t)))
+    if (!devio_range_ok(devio_ask_runtime(d_counts), b->plan->desc.device, d_counts, (uint64_t)b->n_bufs * sizeof(int64_t)))
       return fail(AFX_ERR_INVALID_ARG, "the destination does not lie inside one device allocation on the plan's device");
     const int st = device_sample_rows(b);
     if (st != AFX_OK) return st;
     HIP_TRY(afx::launch_devio_sample_counts(b->d_devio_rows, b->n_bufs, d_counts, b->stream));
   }
-  return hand_over(b, consumer_stream);
+  return devio_hand_over(b, consumer_stream);
 }
 
 }  // extern "C"

@@ -36,6 +36,7 @@ int enqueue_high_level(afx_batch* b, const afx_load_info* levels, const HighBloc
       pairs[2 * i + 1] = levels[i].rms_value;
     }
     HIP_TRY(hipMemcpyAsync(rb.dev + hb.levels, pairs, rb.n * 2 * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    if (rb.uploaded) HIP_TRY(hipEventRecord(rb.uploaded, b->stream));
   }
   HIP_TRY(afx::launch_high_level(a, b->stream));
   return AFX_OK;

@@ -26,6 +26,9 @@
 //                       afx_batch_create_from_raw_device (afx_batch_create_from_raw's plan and steps behind one gather
 //                       launch: batch_create_from_raw_plan below), afx_batch_export_samples_device and its companion
 //                       (DESIGN 4.21); planned in devio/afx_devio_raw_plan.h, launchers in devio/afx_devio_raw.h
+//   afx_device_file_io.cpp  afx_batch_export_file_results_device: what the fetches above a run hand out, into device memory
+//                       of the caller's; planned in devio/afx_devio_file_plan.h, launcher in
+//                       devio/afx_devio_file.h, and none of the files above refers to it
 //   afx_model.cpp       afx_model_create_from_lightgbm / _get_info / _destroy: LightGBM's text into the arrays of
 //                       gbdt/afx_gbdt.h (afx_model.h); no launch
 //
@@ -351,6 +354,14 @@ typedef hipError_t (*RawMove)(const RawPlan& planned, afx_plan* plan, Workspace*
 struct RawMoveStep { RawMove move; void* ctx; };
 int batch_create_from_raw_plan(afx_plan* plan, RawPlan&& planned, const afx_raw* raws, uint32_t mask, RawMove move, void* move_ctx,
                                afx_batch** out_batch, afx_load_info* info);
+
+// ---- afx_device_io.cpp ----
+// What the device-resident exports share (afx_device_file_io.cpp is the other one): what the runtime says of a pointer of
+// the caller's (devio/afx_devio_plan.h compares; nothing is enqueued, nothing is read through it), and the end of every
+// export -- the consumer's stream made to wait for what the batch's stream holds, or the host when there is none.
+struct DevioAlloc;
+DevioAlloc devio_ask_runtime(const void* p);
+int devio_hand_over(afx_batch* b, void* consumer_stream);
 
 }  // namespace host
 }  // namespace afx

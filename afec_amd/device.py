@@ -1,6 +1,7 @@
-"""Device-resident input and output (include/afx.h): batches built from device memory -- normalised mono
-buffers, or raw PCM through the LoadSample front end --, series and the analysed samples exported into device memory.  For
-producers and consumers on the same GPU that this library does not own.
+"""Device-resident input and output (include/afx.h): batches built from device memory -- normalised
+mono buffers, or raw PCM through the LoadSample front end --, series, the analysed samples and the per-file results (high
+level, classification features, class signature) exported into device memory.  For producers and consumers on the same GPU
+that this library does not own.
 
 Device memory is reached through the HIP runtime libafx_hip.so itself is linked against (its symbols are resolved through
 the library's handle: no second runtime is loaded).  Anything that exposes __cuda_array_interface__ -- what ROCm builds of
@@ -37,6 +38,17 @@ class _RawDevice(ctypes.Structure):   # afx_raw_device
                 ("layout", ctypes.c_int32), ("n_frames", ctypes.c_int64), ("channel_stride", ctypes.c_int64)]
 
 
+class _FileDeviceOut(ctypes.Structure):   # afx_file_device_out
+    _fields_ = [("what", ctypes.c_int32), ("dtype", ctypes.c_int32), ("dst", ctypes.c_void_p), ("row_stride", ctypes.c_int64),
+                ("buf_stride", ctypes.c_int64)]
+
+
+# kinds of afx_file_device_out.what (AFX_FILE_*), by number
+FILE_KINDS = ["high_scalars", "spectrum_signature", "pitch", "peak", "features", "features_normalised", "class_signature", "non_finite"]
+FILE_KIND_INDEX = {name: i for i, name in enumerate(FILE_KINDS)}
+FILE_MAX_OUTS = 16
+SIGNATURE_WIDTH = capi.HL_SIGNATURE_FRAMES * capi.HL_SIGNATURE_BANDS
+
 RAW_INTERLEAVED, RAW_PLANAR = 0, 1
 RAW_TILE_FRAMES = 2048   # kDevioRawTileFrames (csrc/devio/afx_devio_raw.h): sample frames one workgroup of the gather moves
 SAMPLE_TILE = 4096       # kDevioSampleTile: elements of a row one workgroup of the sample export writes
@@ -67,6 +79,8 @@ def hip():
                                                        ctypes.POINTER(capi._LoadInfo)]
         L.afx_batch_export_samples_device.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, vp]
         L.afx_batch_export_sample_counts_device.argtypes = [vp, vp, vp]
+        L.afx_batch_export_file_results_device.argtypes = [vp, ctypes.POINTER(capi._LoadInfo), vp, ctypes.POINTER(_FileDeviceOut), ctypes.c_int32,
+                                                           ctypes.c_int32, ctypes.c_int64, ctypes.c_double, vp]
         _hip = L
     return _hip
 
@@ -428,4 +442,92 @@ def frame_counts(batch, stream=None):
     H = hip()
     a = DeviceArray((batch.n_bufs,), np.int64)
     capi._check(H, H.afx_batch_export_frame_counts_device(batch.h, a.ptr, _stream_handle(stream)))
+    return a
+
+
+def _file_kind_numbers(kinds):
+    return [FILE_KIND_INDEX[k] if isinstance(k, str) else int(k) for k in kinds]
+
+
+def _file_kind_shape(kind, model):
+    """the shape of one file's row of a per-file kind"""
+    name = FILE_KINDS[kind]
+    if name == "high_scalars":
+        return (capi.NUM_HL_SCALARS,)
+    if name == "spectrum_signature":
+        return (capi.HL_SIGNATURE_FRAMES, capi.HL_SIGNATURE_BANDS)
+    if name in ("features", "features_normalised"):
+        return (capi.NUM_CLASSIFICATION_FEATURES,)
+    if name == "class_signature":
+        if model is None:
+            raise ValueError("the class signature needs a model")
+        return (model.n_classes,)
+    return ()
+
+
+def file_results_into(batch, outs, model=None, levels=None, layout=EXPORT_PADDED, max_frames=0, pad=0.0, stream=None):
+    """afx_batch_export_file_results_device as the C call takes it.  outs: list of (destination, AFX_FILE_* number, PCM_*
+    code, row_stride, buf_stride); a destination is a DeviceArray (or anything with __cuda_array_interface__) or a pointer.
+    levels: the load-info dicts Plan.batch_from_raw returned, as Batch.fetch_high_level takes them."""
+    H = hip()
+    arr = (_FileDeviceOut * max(1, len(outs)))()
+    for k, (dst, what, code, row_stride, buf_stride) in enumerate(outs):
+        ptr = dst.__cuda_array_interface__["data"][0] if hasattr(dst, "__cuda_array_interface__") else dst
+        arr[k].what, arr[k].dtype, arr[k].dst, arr[k].row_stride, arr[k].buf_stride = what, code, ptr or None, row_stride, buf_stride
+    info = None
+    if levels is not None:
+        if len(levels) != batch.n_bufs:
+            raise ValueError("levels must hold one load info per buffer")
+        info = (capi._LoadInfo * max(1, batch.n_bufs))()
+        for i, d in enumerate(levels):
+            info[i].peak_value, info[i].rms_value = d["peak_value"], d["rms_value"]
+    capi._check(H, H.afx_batch_export_file_results_device(batch.h, info, model.h if model is not None else None, arr, len(outs), layout,
+                                                          max_frames, pad, _stream_handle(stream)))
+
+
+def file_results(batch, kinds, model=None, levels=None, dtype=np.float32, layout="padded", pad=0.0, stream=None, max_frames=None):
+    """The per-file results of a batch that has run -- what Batch.fetch_high_level, fetch_classification_features and
+    fetch_class_signature return on the host -- each into a new DeviceArray, by ONE afx_batch_export_file_results_device
+    call -> dict by kind name (FILE_KINDS): "high_scalars" [n_bufs, 15], "spectrum_signature" [n_bufs, 64, 14], "features"
+    and "features_normalised" [n_bufs, 1680], "class_signature" [n_bufs, n_classes], "non_finite" int32 [n_bufs]; the
+    tracks "pitch" and "peak" [F] packed, [n_bufs, max_frames] padded with `pad` behind a file's frames (max_frames: the
+    longest file's unless given).  model: a capi.Model, for the two kinds that need one.  stream: the consumer's (the call
+    then does not wait for the kernels on the host); None: the data is there on return."""
+    code, numbers = _dtype_code(dtype), _file_kind_numbers(kinds)
+    padded = _LAYOUTS[layout] == EXPORT_PADDED
+    frames = 0
+    if any(FILE_KINDS[k] in ("pitch", "peak") for k in numbers):
+        fo, _ = frame_offsets(batch)
+        frames = int(fo[-1])
+        if max_frames is None:
+            max_frames = int(np.diff(fo).max()) if batch.n_bufs else 0
+    max_frames = int(max_frames or 0)
+    res, outs = {}, []
+    for k in numbers:
+        name = FILE_KINDS[k]
+        if name in ("pitch", "peak"):
+            a = DeviceArray((batch.n_bufs, max_frames) if padded else (frames,), dtype)
+            outs.append((a.ptr or 1, k, code, 1, max_frames))
+        else:
+            row = _file_kind_shape(k, model)
+            a = DeviceArray((batch.n_bufs,) + row, np.int32 if name == "non_finite" else dtype)
+            outs.append((a.ptr or 1, k, code, int(np.prod(row, dtype=np.int64)), 0))
+        res[name] = a
+    file_results_into(batch, outs, model, levels, _LAYOUTS[layout], max_frames if padded else 0, pad, stream)
+    return res
+
+
+def embedding(batch, model=None, normalised=True, dtype=np.float32, stream=None):
+    """The spectrum signature and the classification features of every file side by side as ONE [n_bufs, 896 + 1680]
+    DeviceArray, filled by a single afx_batch_export_file_results_device call whose two destinations are column slices of
+    it (row_stride = 2 576).  normalised: the features as the model's trees read them (needs `model`); False: as fetched.
+    The array's `columns` says where each lies: {kind name: (first column, width)}."""
+    code = _dtype_code(dtype)
+    feature_kind = "features_normalised" if normalised else "features"
+    total = SIGNATURE_WIDTH + capi.NUM_CLASSIFICATION_FEATURES
+    a = DeviceArray((batch.n_bufs, total), dtype)
+    second = a.ptr + SIGNATURE_WIDTH * a.dtype.itemsize if a.ptr else 1
+    file_results_into(batch, [(a.ptr or 1, FILE_KIND_INDEX["spectrum_signature"], code, total, 0),
+                              (second, FILE_KIND_INDEX[feature_kind], code, total, 0)], model, None, EXPORT_PACKED, 0, 0.0, stream)
+    a.columns = {"spectrum_signature": (0, SIGNATURE_WIDTH), feature_kind: (SIGNATURE_WIDTH, capi.NUM_CLASSIFICATION_FEATURES)}
     return a

@@ -659,6 +659,57 @@ int afx_model_evaluate_features(const afx_model* model, const double* features /
                                 int32_t n_vectors, float* signature /* [n_vectors][n_classes] */,
                                 int32_t* iterations_used /* [n_vectors][n_models] or NULL */, int32_t* non_finite /* [n_vectors] or NULL */);
 
+/* ---- the per-file results into device memory ----
+ * What the three fetches above hand out on the host -- afx_batch_fetch_high_level, afx_batch_fetch_classification_features,
+ * afx_batch_fetch_class_signature -- written into device memory of the caller's instead, the same bits, for a consumer on
+ * the same GPU (a similarity index over spectrum signatures, a classifier fed the normalised features).  The call launches
+ * only the kernels its destinations need (the fetches' own, on the batch's stream, into the batch's result block) and
+ * behind them ONE launch that scatters the block into all destinations; nothing is downloaded.  Additive: every other
+ * entry point launches what it launched before. */
+#define AFX_FILE_HIGH_SCALARS         0  /* W = AFX_NUM_HL_SCALARS, as afx_high_out.scalars, per file          */
+#define AFX_FILE_SPECTRUM_SIGNATURE   1  /* W = 64 * 14, [frame][band] as afx_high_out.signature               */
+#define AFX_FILE_PITCH                2  /* per-frame track, W = 1, as afx_high_out.pitch                      */
+#define AFX_FILE_PEAK                 3  /* per-frame track, W = 1, as afx_high_out.peak                       */
+#define AFX_FILE_FEATURES             4  /* W = AFX_NUM_CLASSIFICATION_FEATURES, as fetched                    */
+#define AFX_FILE_FEATURES_NORMALISED  5  /* the same as the model's trees read them (needs model)              */
+#define AFX_FILE_CLASS_SIGNATURE      6  /* W = the model's n_classes, float (needs model)                     */
+#define AFX_FILE_NON_FINITE           7  /* W = 1, int32 per file, as the feature fetch counts it              */
+#define AFX_NUM_FILE_KINDS            8
+#define AFX_FILE_MAX_OUTS            16  /* destinations of one call: every kind as float and as double        */
+typedef struct afx_file_device_out {
+  int32_t what;        /* AFX_FILE_* */
+  int32_t dtype;       /* AFX_PCM_F32 | AFX_PCM_F64; ignored for AFX_FILE_NON_FINITE (int32)                          */
+  void*   dst;         /* device memory on the plan's device                                                           */
+  int64_t row_stride;  /* elements between files (per-file kinds, >= W); between frames (tracks, >= 1)                 */
+  int64_t buf_stride;  /* tracks in the padded layout only: elements between files                                     */
+} afx_file_device_out;
+/* After afx_batch_run, any number of times.  AFX_PCM_F64: the bits of the fetch (the float class signature widened, which
+ * is exact); AFX_PCM_F32: (float) of them, round to nearest even.  AFX_FILE_FEATURES_NORMALISED is
+ * clamp(features * scale + offset, -limits, +limits) with the product rounded before the sum and the two comparisons in
+ * the order of the models' kernel (std::min(limit, y) then std::max(-limit, y): a NaN becomes -limit); a buffer without
+ * frames or refused has the zeros of the feature fetch, normalised like any other value, i.e. clamp(0 * scale + offset).
+ * AFX_FILE_NON_FINITE counts the raw features.  Per-file kinds: file i's row at dst + i x row_stride, of which W elements
+ * are written.  The tracks follow afx_batch_export_device's layouts: AFX_EXPORT_PACKED, frame r of the batch at dst + r x
+ * row_stride; AFX_EXPORT_PADDED, frame f of file i at dst + i x buf_stride + f x row_stride, with pad_value (as there) in
+ * the rows at and behind the file's frame count up to max_frames.  layout, max_frames and pad_value concern the tracks only
+ * (the layout must still be one of the two).  levels: as afx_batch_fetch_high_level; model: as
+ * afx_batch_fetch_class_signature, NULL unless a destination needs it.  consumer_stream: as afx_batch_export_device --
+ * non-NULL, that stream is made to wait for the launch and the call returns once its small uploads (levels, effective
+ * lengths, statuses) have left the host's staging memory, not when the kernels have run; NULL, it returns when the data is
+ * there.  n_bufs == 0: AFX_OK, nothing launched.
+ * AFX_ERR_INVALID_ARG, with nothing enqueued and a text that names the destination: before the first run; a kind whose
+ * inputs the batch's mask lacks (AFX_D_HIGH_LEVEL_INPUTS for kinds 0..3, AFX_D_CLASSIFICATION_INPUTS for 4..7); a kind that
+ * needs a model without one, or a model on another device; more than AFX_FILE_MAX_OUTS destinations; an unknown what,
+ * dtype or layout; a NULL dst; a row_stride below W; padded tracks: max_frames below the longest file's frames or a
+ * buf_stride below max_frames x row_stride; a destination whose extent -- (n_bufs - 1) x row_stride + W elements per file,
+ * the tracks' as afx_batch_export_device states them -- overflows or does not lie inside ONE device allocation on the
+ * plan's device. */
+int afx_batch_export_file_results_device(afx_batch* batch, const afx_load_info* levels /* [n_bufs] or NULL */,
+                                         const afx_model* model /* NULL unless a destination needs it */,
+                                         const afx_file_device_out* outs, int32_t n_outs,
+                                         int32_t layout /* tracks: AFX_EXPORT_PACKED | AFX_EXPORT_PADDED */, int64_t max_frames,
+                                         double pad_value, void* consumer_stream);
+
 /* ---- class decision: what the reference makes of the signatures, SampleAnalyser.cpp:1097-1231 ---- *
  * The columns a reader of the reference's high-level database sees -- class_strengths, classes, category_signature,
  * category_strengths, categories -- from the class signature above, formed on the device in the reference's order:
